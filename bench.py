@@ -15,6 +15,12 @@ under torch.distributed.run; a plain `python bench.py --gpus N` starts that
 launcher itself as a child process before anything touches the GPU.
 
 value = sum of parsed block bytes over all ranks / max-over-ranks wall time.
+
+A plain run sets up, warms up, times `--steps` steps, writes the last step's
+outputs if `--dump-outputs DIR` is given, and prints the result line.  `--full`
+adds what takes passes of its own after the timed region: the closed-form
+check of every descriptor, the roofline's event-timed kernel passes, the
+cold-input pass and the CPU baseline.
 """
 import argparse
 import json
@@ -38,6 +44,8 @@ CONFIG4_GLOBAL_BLOCKS = 1_000_000  # BASELINE.json configs[3]
 METRIC = "GiB/s of device-resident .sst data-block bytes decoded to KV records"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, MI355X_MICROARCH.md
 GIB = float(1 << 30)
+DUMP_CONFIGS = ("decode4k", "decode64k", "mixed", "wal")
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
 
 
 def parse(argv=None):
@@ -56,13 +64,22 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher and deal only (gloo, no device work): prints the deal")
     ap.add_argument("--arena", action="store_true", help="materialize keys/values too")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps also run what takes passes of its own: the "
+                         "closed-form check of the timed output, the roofline's kernel times, "
+                         "the cold-input pass and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as "
+                         "DIR/<name>.npy (block-decode configs; see decode_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--placement", default="offset", choices=["offset", "plan"],
                     help="decode output placement: offset-addressed (no plan) or dense "
                          "(lsm_plan_* inside every step)")
     ap.add_argument("--no-cold", action="store_true",
-                    help="skip the cold-input pass (input rotated over copies the MALL cannot hold)")
+                    help="with --full: skip the cold-input pass (input rotated over copies the "
+                         "MALL cannot hold)")
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the post-timing output check (diagnostic library variants only)")
     ap.add_argument("--e2e", action="store_true",
@@ -76,7 +93,11 @@ def parse(argv=None):
     ap.add_argument("--tie", default="input", choices=["input", "goheap"],
                     help="--config compact: equal keys in input order (LSM_TIE_INPUT) or in "
                          "container/heap's pop order, the reference's exact output (LSM_TIE_GOHEAP)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.e2e or args.config not in DUMP_CONFIGS):
+        ap.error("--dump-outputs covers the block-decode lines only: --config "
+                 + " | ".join(DUMP_CONFIGS) + ", without --e2e")
+    return args
 
 
 def _free_port():
@@ -305,6 +326,46 @@ def bench_decode(args, world, rank, local):
     # correctness gate on the timed output: every block decoded cleanly
     assert int((r.status[:nblk] != 0).sum()) == 0, "decode reported errors"
     nrec_total = int(r.nrec[:nblk].sum().item())
+    if args.dump_outputs:
+        # what the last timed step left in the outputs, before any further launch
+        dump_outputs(args.dump_outputs, rank, world,
+                     decode_outputs(args, r, d_off, blk_len, nblk))
+    parsed = float(blk_len.astype(np.float64).sum())
+    parsed_all = sum_over_ranks(world, parsed)
+    value = parsed_all * args.steps / elapsed / GIB
+    scaling = block_ids_for(args, world, rank)[1] if args.config in UNIFORM else "weak"
+    out = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 5),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (seed 0x5EED, keys k%015d, splitmix64 values)",
+        "verified": "status 0 for every block of the timed output (--full: every descriptor)",
+        "config": {
+            "workload": wdesc,
+            "grammar": "KV (kv/kv.go:46-115)",
+            "output": "ARENA (descriptors + packed keys/values)" if args.arena else
+                      "DESC (16 B record descriptors)",
+            "blocks_per_gpu": int(nblk),
+            "records_per_gpu": nrec_total,
+            "parsed_bytes_per_gpu": int(parsed),
+            "parallelism": (f"dp{world} (logs per rank, no collective)" if args.config == "wal" else
+                            f"dp{world} (blocks round-robin, no collective)"),
+            **({"scaling_note": "weak, per-rank copy: every rank replays its own log set"}
+               if args.config == "wal" else {}),
+        },
+    }
+    if not args.full:
+        return out, (buf, blk_off, blk_len)
+
+    # --full: everything below takes launches of its own, after the timed region.
     # kernel time from HIP events, in passes of their own: an event pair
     # around every launch puts a ~10 us marker gap between launches
     # (profiles/r03_ktrace_events.txt), so the wall-timed loop has none
@@ -312,13 +373,10 @@ def bench_decode(args, world, rank, local):
     # the timed output is checked after the timed region: the line fails on a
     # single wrong descriptor (kv/kv.go:77-115 record chain, closed form)
     verify_decode(args, r, d_off, d_len, nblk)
+    out["verified"] = "every record descriptor, nrec and status of the timed output (closed form)"
 
-    parsed = float(blk_len.astype(np.float64).sum())
     cold = (cold_input_pass(args, ctx, buf, d_off, d_len, nblk, hint, stream, parsed)
             if args.config in UNIFORM and not args.no_cold and args.placement == "offset" else None)
-    parsed_all = sum_over_ranks(world, parsed)
-    value = parsed_all * args.steps / elapsed / GIB
-    scaling = block_ids_for(args, world, rank)[1] if args.config in UNIFORM else "weak"
 
     # algorithmic bytes of one launch: block bytes +
     # per-block metadata (blk_off 8 + blk_len 4) read; 16 B per record
@@ -336,48 +394,20 @@ def bench_decode(args, world, rank, local):
         traffic, tsrc = None, "not calibrated for the scheduled mixed-size pattern (DESIGN.md §7)"
     if cold is not None:
         cold["frac"] = round(alg / (cold["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    out = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "GiB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 5),
-        "higher_is_better": True,
-        "scaling": scaling,
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (seed 0x5EED, keys k%015d, splitmix64 values)",
-        "verified": "every record descriptor, nrec and status of the timed output (closed form)",
-        "config": {
-            "workload": wdesc,
-            "grammar": "KV (kv/kv.go:46-115)",
-            "output": "ARENA (descriptors + packed keys/values)" if args.arena else
-                      "DESC (16 B record descriptors)",
-            "blocks_per_gpu": int(nblk),
-            "records_per_gpu": nrec_total,
-            "parsed_bytes_per_gpu": int(parsed),
-            "parallelism": (f"dp{world} (logs per rank, no collective)" if args.config == "wal" else
-                            f"dp{world} (blocks round-robin, no collective)"),
-            **({"scaling_note": "weak, per-rank copy: every rank replays its own log set"}
-               if args.config == "wal" else {}),
-        },
-        "roofline": {
-            "bound": "hbm",
-            "kernel": decode_kernel_label(args),
-            "achieved": round(achieved, 1),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "traffic": traffic,
-            "traffic_source": tsrc,
-            "alg_bytes_per_launch": int(alg),
-            "kernel_ms": round(kern_ms, 5),
-            "kernel_ms_source": KERNEL_MS_SOURCE,
-            "kernel_ms_median": round(float(np.median(times)), 5),
-            "kernel_ms_min": round(float(times.min()), 5),
-        },
+    out["roofline"] = {
+        "bound": "hbm",
+        "kernel": decode_kernel_label(args),
+        "achieved": round(achieved, 1),
+        "peak": HBM_PEAK_GBS,
+        "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": traffic,
+        "traffic_source": tsrc,
+        "alg_bytes_per_launch": int(alg),
+        "kernel_ms": round(kern_ms, 5),
+        "kernel_ms_source": KERNEL_MS_SOURCE,
+        "kernel_ms_median": round(float(np.median(times)), 5),
+        "kernel_ms_min": round(float(times.min()), 5),
     }
     if cold is not None:
         out["cold_input"] = cold
@@ -547,6 +577,65 @@ def verify_decode(args, r, d_off, d_len, nblk):
                                    recs_in[:, :, 24:124]), "arena: values"
             assert bool(((klen == 16) & (vlen == 100)).all()), "decode: record lengths"
             assert bool((rec_off == off[blk] + 124 * j).all()), "decode: record offsets"
+
+
+def decode_outputs(args, r, d_off, blk_len, nblk):
+    """What a caller of the timed decode receives, as float arrays (--dump-outputs).
+
+    nrec and status of every block (float32).  The record descriptors are
+    offset-addressed (or dense behind rec_base) and fill GBs with their unused
+    slots, so they are written for a sample of blocks only: a seeded
+    permutation of the block ids, cut where the bound on the sample's bytes --
+    from the input lengths alone, so the same blocks for any build -- reaches
+    what DUMP_LIMIT leaves.  For the sampled blocks, in ascending block order, every
+    record in block order: desc_rec_off (float64: offsets pass 2^24),
+    desc_key_len, desc_val_len (float32); with --arena the blocks' packed key
+    and value bytes (float32).  sample_blocks holds the block ids."""
+    dev = r.nrec.device
+    out = {"nrec": r.nrec[:nblk].cpu().numpy().astype(np.float32),
+           "status": r.status[:nblk].cpu().numpy().astype(np.float32)}
+    ln = blk_len[:nblk].astype(np.int64)
+    arena = r.key_arena is not None or r.val_arena is not None
+    # <= len / 8 records of 16 B (f64 + 2 x f32) each, <= len arena bytes as f32
+    bound = 2 * ln + (4 * ln if arena else 0) + 8
+    perm = np.random.default_rng(synth.SEED).permutation(nblk)
+    budget = DUMP_LIMIT - 8 * nblk  # nrec and status come first
+    k = int(np.searchsorted(np.cumsum(bound[perm]), budget, side="right"))
+    sample = np.sort(perm[:k])
+    out["sample_blocks"] = sample.astype(np.float64)
+    s = torch.from_numpy(sample).to(dev)
+    off = d_off.to(torch.int64)
+    base = (r.rec_base[:nblk].to(torch.int64) if r.rec_base is not None
+            else off // lsmgpu.codec.MIN_RECORD[lsmgpu.GRAMMAR_KV])
+    n = r.nrec[:nblk].to(torch.int64)[s]
+    first = torch.cumsum(n, 0) - n
+    blk = torch.repeat_interleave(torch.arange(k, device=dev), n)
+    j = torch.arange(int(n.sum()), device=dev) - first[blk]
+    d = r.desc[base[s][blk] + j].to(torch.int64)
+    klen, vlen = d[:, 2] & 0xFFFFFFFF, d[:, 3] & 0xFFFFFFFF
+    out["desc_rec_off"] = ((d[:, 0] & 0xFFFFFFFF) | (d[:, 1] << 32)).cpu().numpy().astype(np.float64)
+    out["desc_key_len"] = klen.cpu().numpy().astype(np.float32)
+    out["desc_val_len"] = vlen.cpu().numpy().astype(np.float32)
+    abase = (r.arena_base[:nblk].to(torch.int64) if r.arena_base is not None else off)[s]
+    for name, arr, flen in (("key_arena", r.key_arena, klen), ("val_arena", r.val_arena, vlen)):
+        if arr is None:
+            continue
+        # block b's fields lie packed from its arena base
+        per = torch.zeros(k, dtype=torch.int64, device=dev).index_add_(0, blk, flen)
+        owner = torch.repeat_interleave(torch.arange(k, device=dev), per)
+        pos = torch.arange(int(per.sum()), device=dev) - (torch.cumsum(per, 0) - per)[owner]
+        out[name] = arr[abase[owner] + pos].cpu().numpy().astype(np.float32)
+    return out
+
+
+def dump_outputs(path, rank, world, arrays):
+    """DIR/<name>.npy, one file per array (N > 1: <name>_rank<r>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64)
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 
@@ -795,9 +884,9 @@ def main(argv=None):
         out, data = bench_compact(args, world, rank, local)
     else:
         out, data = bench_decode(args, world, rank, local)
-    # the CPU baseline on rank 0, after every rank's timed region (at N > 1
-    # over rank 0's shard: the same sample shape as at N = 1)
-    if rank == 0 and not args.no_cpu_baseline:
+    # --full: the CPU baseline on rank 0, after every rank's timed region (at
+    # N > 1 over rank 0's shard: the same sample shape as at N = 1)
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if args.config == "sst":
             from bench_sst import cpu_baseline_sst
             out["cpu_baseline"] = cpu_baseline_sst(args, data)

@@ -11,4 +11,4 @@ L.LIB_PATH = os.path.abspath(sys.argv[1])
 L.CHECK_BUILD_ID = False  # a patched variant: not built from the tree's sources
 import bench  # noqa: E402
 
-bench.main(["--no-cpu-baseline"] + sys.argv[2:])
+bench.main(["--full", "--no-cpu-baseline"] + sys.argv[2:])

@@ -8,8 +8,9 @@ timeout -k 10 900 python -u -m pytest ${TESTS-tests/test_stream_build_gpu.py} -m
 tail -2 gpurun_out/${T}_pytest.log
 fi
 for L in ${LINES:-sst}; do
-timeout -k 10 300 python bench.py --config $L --cpu-seconds ${CPUS:-3} > gpurun_out/${T}_bench_$L.json 2> gpurun_out/${T}_bench_$L.err || { tail -20 gpurun_out/${T}_bench_$L.err; exit 1; }
-cut -c1-700 gpurun_out/${T}_bench_$L.json
+B=${OUT:-evidence_out}/${T}_bench_$L; mkdir -p ${OUT:-evidence_out}
+timeout -k 10 300 python bench.py --full --config $L --cpu-seconds ${CPUS:-3} > $B.json 2> $B.err || { tail -20 $B.err; exit 1; }
+cut -c1-700 $B.json
 done
 for P in ${PROF-sst}; do
 TESTS= LINES= CFG=$P TAG=$T bash scripts/gpu_quick.sh 2>/dev/null

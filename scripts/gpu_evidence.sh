@@ -30,7 +30,7 @@ DA[d64]="--config decode64k"; DK[d64]=decode64k:6400:desc
 for t in ${PMC1-desc arena d64}; do
   for c in FETCH_SIZE WRITE_SIZE; do
     step pmc_${t}_$c 180 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc_${TAG}_${t}_$c -o run \
-      -- python bench.py ${DA[$t]} --steps 5 --warmup 2 --no-cpu-baseline --no-cold > $OUT/pmc_${TAG}_${t}_$c.log 2>&1 || exit 1
+      -- python bench.py --full ${DA[$t]} --steps 5 --warmup 2 --no-cpu-baseline --no-cold > $OUT/pmc_${TAG}_${t}_$c.log 2>&1 || exit 1
   done
   python scripts/pmc_summary.py $OUT/pmc_${TAG}_${t}_FETCH_SIZE $OUT/pmc_${TAG}_${t}_WRITE_SIZE decode_v2_kernel \
     ${DK[$t]} $OUT/${TAG}_pmc_$t.json > /dev/null && cp $OUT/${TAG}_pmc_$t.json profiles/ || exit 1
@@ -50,7 +50,7 @@ for cfg in ${PMCM-sst sstdec probe wal}; do
   SK=0; [ $cfg = compact ] && SK=1  # the input images' decode before the steps
   for c in FETCH_SIZE WRITE_SIZE; do
     step pmcm_${cfg}_$c 180 rocprofv3 --pmc $c --output-format csv -d $OUT/pmcm_${TAG}_${cfg}_$c -o run \
-      -- python bench.py --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --no-cold > $OUT/pmcm_${TAG}_${cfg}_$c.log 2>&1 || exit 1
+      -- python bench.py --full --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --no-cold > $OUT/pmcm_${TAG}_${cfg}_$c.log 2>&1 || exit 1
   done
   SKIP_ANCHORS=$SK python scripts/pmc_multi.py $OUT/pmcm_${TAG}_${cfg}_FETCH_SIZE $OUT/pmcm_${TAG}_${cfg}_WRITE_SIZE "${K[$cfg]}" "${A[$cfg]}" "${W[$cfg]}" \
     profiles/${TAG}_pmc_$cfg.json $OUT/${TAG}_pmc_$cfg.json > /dev/null || exit 1
@@ -65,14 +65,14 @@ for line in ${LINES:-decode4k cfg4 decode64k mixed arena sst sstdec sstdec1 wal 
     goheap) args="--config compact --tie goheap --steps 5 --warmup 1" ;;
     *) args="--config $line" ;;
   esac
-  step bench_$line 600 python bench.py $args > $OUT/bench_${TAG}_$line.json 2> $OUT/bench_${TAG}_$line.err \
+  step bench_$line 600 python bench.py --full $args > $OUT/bench_${TAG}_$line.json 2> $OUT/bench_${TAG}_$line.err \
     || { tail -20 $OUT/bench_${TAG}_$line.err; exit 1; }
   cut -c1-200 $OUT/bench_${TAG}_$line.json
 done
 for p in ${PROF:-decode4k arena decode64k mixed sst sstdec probe level get get0 wal compact}; do
   case $p in arena) args="--arena" ;; *) args="--config $p" ;; esac
   step prof_$p 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$p -o run \
-    -- python bench.py $args --steps 20 --warmup 3 --no-cpu-baseline --no-cold > $OUT/prof_${TAG}_$p.log 2>&1 || exit 1
+    -- python bench.py --full $args --steps 20 --warmup 3 --no-cpu-baseline --no-cold > $OUT/prof_${TAG}_$p.log 2>&1 || exit 1
 done
 fi
 echo "== done $(date +%T)"

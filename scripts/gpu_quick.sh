@@ -14,8 +14,9 @@ if [ -n "$LINES" ]; then
   VARIANTS="${VARIANTS:-prod}" REPS=${REPS:-2} STEPS=${STEPS:-50} bash scripts/ab_pair.sh || exit 1
 fi
 if [ -n "$CFG" ]; then
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_${TAG}_$CFG -o run \
-    -- python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-cold > gpurun_out/prof_${TAG}_$CFG.log 2>&1 \
-    || { tail -20 gpurun_out/prof_${TAG}_$CFG.log; exit 1; }
-  python scripts/kstats.py gpurun_out/prof_${TAG}_$CFG/run_kernel_stats.csv 63 | head -12 || true
+  P=${OUT:-evidence_out}/prof_${TAG}_$CFG; mkdir -p ${OUT:-evidence_out}
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P -o run \
+    -- python bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-cold > $P.log 2>&1 \
+    || { tail -20 $P.log; exit 1; }
+  python scripts/kstats.py $P/run_kernel_stats.csv 63 | head -12 || true
 fi

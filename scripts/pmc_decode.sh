@@ -13,7 +13,7 @@ set -- "$G1" "$G2"
 [ -n "$PMC_LDS" ] && set -- "$G1" "$G2" "$G3"
 for grp in "$@"; do
   i=$((i+1))
-  timeout -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d $OUTD/p$i -o run -- python ${PYCMD:-bench.py} ${BENCH_ARGS:---config $CFG} ${PYARGS:---steps 3 --warmup 1 --no-cpu-baseline} > $OUTD/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUTD/p$i.log; exit 1; }
+  timeout -s KILL 120 rocprofv3 --pmc $grp --output-format csv -d $OUTD/p$i -o run -- python ${PYCMD:-bench.py} ${BENCH_ARGS:---config $CFG} ${PYARGS:---full --steps 3 --warmup 1 --no-cpu-baseline} > $OUTD/p$i.log 2>&1 || { echo "pass $i failed"; tail -5 $OUTD/p$i.log; exit 1; }
 done
 OUTD=$OUTD KF=$KF python - <<'PY'
 import csv, glob, collections, os

@@ -594,9 +594,14 @@ def test_compact_merge_matches_two_calls_small(ctx, tie):
     kd, vd, prefix = lsmgpu.sst_pairs(ctx, r)
     n = int(kd.shape[0])
     cap = int(r.idx_desc.shape[0])
+    assert cap > n + 1
     for bad in (n + 1, n - 1, 0):
-        kd2 = torch.empty((cap, 4), dtype=torch.int32, device=ctx.torch_device)
-        vd2 = torch.empty((cap, 4), dtype=torch.int32, device=ctx.torch_device)
+        # zeroed, not torch.empty: the key statistics run over `bad` pairs before
+        # the count is read back and refused, so slot n (which the join does not
+        # write) is read as a descriptor; whatever the allocator left there would
+        # be followed as a key offset.  A zero descriptor is an empty key.
+        kd2 = torch.zeros((cap, 4), dtype=torch.int32, device=ctx.torch_device)
+        vd2 = torch.zeros((cap, 4), dtype=torch.int32, device=ctx.torch_device)
         pre2 = torch.empty((r.nfile + 1,), dtype=torch.int64, device=ctx.torch_device)
         mg = lsmgpu.alloc_merge(ctx, max(bad, 1))
         mg.n = bad
