@@ -7,7 +7,9 @@
 // past its padded end).  Record boundaries are a dependent chain (each
 // position depends on every earlier length, data.go:58-76): the wave verifies
 // 64 records at a time by speculative runs and chases the rest exactly on
-// the VALU (decode_range_v2).  Descriptors leave as coalesced 16-byte stores;
+// the VALU (decode_range_v2); a DESC block that fits the ring is landed in one
+// burst and starts with one run from record 0 (decode_block_lin).
+// Descriptors leave as coalesced 16-byte stores;
 // in ARENA mode the key and value bytes are gathered from the LDS ring into
 // packed arenas with 16-byte stores (the bytes Go's make()+ReadFull produce).
 // Also here: the whole-.sst decode (f1), WAL replay (f4) and the dense
@@ -44,6 +46,23 @@ struct RingPolicy {
     static constexpr int load_aux = ((ARENA || BIG) && NCH == 8) ? 0 : kBlockLoadAux;
     static constexpr bool nt_desc = NCH == 8;
 };
+// LDS held beside the 8 KiB ring by the DESC kernel of a launch whose caller
+// declared blocks of 3 KiB to the ring's size (lsm_decode_blocks_hinted): 12
+// KiB per one-wave workgroup, 13 waves per CU instead of 19.  Measured, on one
+// box (boxes differ by +-4%), config 2 with the straight-line path
+// (decode_block_lin), resident / cold kernel us: 19 waves 83.3 / 83.9, 17:
+// 81.0 / 81.9, 15: 76.6 / 78.3, 14: 75.9 / 78.2, 13: 75.0 / 74.3, 11: 79.8 /
+// 78.8, 9: 83.6 / 84.4, 7: 102.0 / 102.7; the parent's general chase 78.1 /
+// 79.1 at 19 waves, 90.3 / 88.5 at 13.  Inferred from these sweeps, not from a
+// counter: a wave of the straight-line path waits for its block for nearly
+// all its life, and 19 x 4 KiB streams per CU are more than HBM serves well.
+// The pad is fitted to that block size: it loses on blocks of 1-3 KiB (1 KiB:
+// 151.6 against 109.4 us), on streamed blocks (mixed sizes 130.4 against
+// 114.5) and on IDX blocks (120.4 against 117.9), so only a declared bound
+// selects it, and never for IDX.
+constexpr uint32_t kFitPad = 4096;
+constexpr uint32_t kFitMin = 3072;  // a bound above this (3 KiB blocks lose: 85.6 against 78.5 us)
+
 template <uint32_t NCH, bool ARENA>
 __device__ __forceinline__ void store_desc(u32x4 *p, const u32x4 &d) {
     if (RingPolicy<NCH, ARENA>::nt_desc)
@@ -507,11 +526,21 @@ struct ArenaCur {
 // `stop` are not decoded (a clean stop; stop = n decodes the whole range).
 // ARENA: keys and values are also packed into a.key_arena / a.val_arena from
 // the cursors `ac` (tab: the 129-dword LDS table of arena_emit_batch).
-template <int G, uint32_t NCH, bool LIN, bool ARENA = false, bool BIG = false>
+// Where a chase goes on after records verified elsewhere: record nr at block
+// position pos, kprev the last key length (none: 0xFFFFFFFF).
+struct ChaseResume {
+    uint32_t pos = 0, nr = 0, kprev = 0xFFFFFFFFu;
+};
+// PRE: the caller (decode_block_lin) has landed the whole block in the ring
+// and verified the records before rs0.pos: the chase goes on there and loads
+// nothing (the reader only supplies the block's descriptor and start).
+template <int G, uint32_t NCH, bool LIN, bool ARENA = false, bool BIG = false, bool PRE = false>
 __device__ void decode_range_v2(const DecodeArgs &a, uint32_t *ring, uint64_t off, uint32_t n,
                                 uint64_t base, uint32_t ncap, uint32_t &nr_out, int32_t &st_out,
                                 uint32_t stop, uint32_t &pos_out, ArenaCur ac = {},
-                                uint32_t *tab = nullptr, bool lin_rt = LIN) {
+                                uint32_t *tab = nullptr, bool lin_rt = LIN,
+                                const ChaseResume rs0 = {}) {
+    static_assert(!PRE || (LIN && !ARENA), "a pre-landed ring is a DESC block that fits it");
     // the block fits the ring (read linearly, landed whole at the first
     // step): a template constant, or for ARENA a runtime flag (the ring is
     // then always indexed modulo its size, which is the same for such blocks)
@@ -530,7 +559,10 @@ __device__ void decode_range_v2(const DecodeArgs &a, uint32_t *ring, uint64_t of
     };
 
     uint32_t s_pos = 0, s_k = 0, s_v = 0, s_xlo = 0, s_xhi = 0, ns = 0, s_first = 0;
-    uint32_t pos = 0, nr = 0, kprev = 0xFFFFFFFFu, miss = 0, skip = 0;
+    // (a resumed chase starts its back-off afresh, miss = skip = 0, where the
+    // chase from record 0 would carry skip = 1 after a failed first run: the
+    // heuristic only picks which step verifies a record, never the result)
+    uint32_t pos = rs0.pos, nr = rs0.nr, kprev = rs0.kprev, miss = 0, skip = 0;
     // ARENA: the exact step's record (the last staged one) leaves its arena
     // bytes together with the run that follows it (same K, V, stride)
     uint32_t pend = 0, pend_pos = 0, pend_k = 0, pend_v = 0;
@@ -589,9 +621,9 @@ __device__ void decode_range_v2(const DecodeArgs &a, uint32_t *ring, uint64_t of
         }
     };
     // Block bytes below `lim` (and at or above the last anchor) are landed.
-    uint32_t lim = 0;
+    uint32_t lim = PRE ? n : 0;
     auto need = [&](uint32_t p, uint32_t len) {
-        if ((uint64_t)p + len <= lim) return;
+        if (PRE || (uint64_t)p + len <= lim) return;
         // a streamed block recycles ring chunks: the staged records' arena
         // bytes leave first
         if (ARENA && !lin) {
@@ -830,6 +862,112 @@ __device__ void decode_block_v2(const DecodeArgs &a, uint32_t b, uint32_t *ring,
     }
 }
 
+// ---- DESC blocks that fit the ring: the straight-line path -----------------
+//
+// A block with round_up16(h + n) <= ring needs none of the ring's
+// bookkeeping: every chunk's LDS-DMA is issued in one unrolled burst, one
+// vmcnt(0) lands the block, and record 0's fields are read once.  Lane i then
+// tests the record at i * S against record 0's (K, V) straight from LDS (lane
+// 0 is record 0 itself); one ballot gives the verified count j, one store
+// covers the descriptors of records 0..j-1 (config 2: one 528-byte nt store
+// per block, the block's first 128-byte descriptor line written whole).  A
+// run that ends at n finishes the block there.  Anything else (a record 0
+// that fails a check, a mismatch, a run of 64, a truncated tail, capacity)
+// goes on in the general chase at the first unverified record with the ring
+// as landed (PRE): the statuses and the records are the exact step's.
+//
+// Record 0 passes the reference's checks (kv.go:77-115, data.go:58-76,
+// index.go:70-98) exactly when its fields end inside the block: n is at most
+// the ring, far below kKeyCap and kValCap, so the two cap checks cannot fail
+// on a record that fits.
+
+template <int G, uint32_t NCH, bool BIG>
+__device__ __forceinline__ void decode_block_lin(const DecodeArgs &a, uint32_t b, uint32_t *ring,
+                                                 uint64_t off, uint32_t n) {
+    static_assert(NCH * kChunk <= kKeyCap && NCH * kChunk <= kValCap, "caps hold for a block that fits");
+    constexpr int AUX = RingPolicy<NCH, false, BIG>::load_aux;
+    constexpr uint32_t R = MinRecord<G>::R;
+    const uint32_t lane = lane_id();
+    const uint32_t h = (uint32_t)off & 15;
+    const uint32_t total = (h + n + 15) & ~15u;  // <= NCH * kChunk
+    const uint32_t nchunks = (total + kChunk - 1) / kChunk;
+    const rsrc_t rsrc = make_rsrc(a.in + (off - h), total);
+    const uint32_t voff = lane * 16;
+#pragma unroll
+    for (uint32_t c = 0; c < NCH; c++)
+        if (c < nchunks)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(
+                rsrc, (__attribute__((address_space(3))) void *)&ring[c * (kChunk / 4)], 16,
+                voff + c * kChunk, 0, 0, AUX);
+    uint64_t base64, cap64;
+    record_slots<G>(a, b, off, n, base64, cap64);
+    const uint64_t base = uni64(base64);
+    const uint32_t ncap = uni(cap64 < 0xFFFFFFFFull ? (uint32_t)cap64 : 0xFFFFFFFFu);
+    // The DMA writes are invisible to the compiler's waitcnt tracking of
+    // ds_read; wait for them explicitly before any LDS read of them.
+    __asm__ __volatile__("s_waitcnt vmcnt(0)" ::: "memory");
+    const RingBytes<NCH, true> rb{ring, rsrc, 0, 0};
+    uint32_t pos = 0, nr = 0, K = 0, V = 8;
+    if (n >= R) {
+        bool ok0;
+        if (G == LSM_GRAMMAR_V) {
+            V = uni(rb.u32(h));
+            ok0 = V <= n - 4;
+        } else if (G == LSM_GRAMMAR_KV) {
+            K = uni(rb.u32(h));
+            ok0 = K <= n - 8;
+            if (ok0) {
+                V = uni(rb.u32(h + 4 + K));
+                ok0 = V <= n - 8 - K;
+            }
+        } else {
+            K = uni(rb.u32(h));
+            ok0 = K <= n - 12;
+        }
+        if (ok0) {
+            const uint32_t S = G == LSM_GRAMMAR_V ? 4 + V : G == LSM_GRAMMAR_KV ? 8 + K + V : 12 + K;
+            const uint32_t p = lane * S;  // S <= n <= 16 KiB: no overflow
+            bool ok = p + S <= n && lane < ncap;
+            uint64_t xx = 0;
+            if (ok) {
+                if (G == LSM_GRAMMAR_V) {
+                    ok = rb.u32(h + p) == V;
+                } else if (G == LSM_GRAMMAR_KV) {
+                    ok = (int)(rb.u32(h + p) == K) & (int)(rb.u32(h + p + 4 + K) == V);
+                } else {
+                    ok = rb.u32(h + p) == K;
+                    xx = (uint64_t)rb.u32(h + p + 8 + K) << 32 | rb.u32(h + p + 4 + K);
+                }
+            }
+            const uint64_t m = __ballot(ok);
+            const uint32_t j = m == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~m);
+            if (lane < j) {
+                const uint64_t ro = off + p;
+                u32x4 d;
+                d.x = (uint32_t)ro;
+                d.y = (uint32_t)(ro >> 32);
+                d.z = K;
+                d.w = V;
+                store_desc<NCH, false>(&a.desc[base + lane], d);
+                if (G == LSM_GRAMMAR_IDX && a.idx_value) a.idx_value[base + lane] = (int64_t)xx;
+            }
+            nr = j;
+            pos = j * S;
+        }
+    }
+    int32_t st = LSM_OK;
+    if (pos != n) {
+        uint32_t end;
+        decode_range_v2<G, NCH, true, false, BIG, true>(
+            a, ring, off, n, base, ncap, nr, st, n, end, {}, nullptr, true,
+            ChaseResume{pos, nr, G == LSM_GRAMMAR_KV && nr ? K : 0xFFFFFFFFu});
+    }
+    if (lane == 0) {
+        a.nrec[b] = nr;
+        a.status[b] = st;
+    }
+}
+
 // Either form of the range decoder: linear when the range fits the ring.
 template <int G, uint32_t NCH>
 __device__ void decode_range_any(const DecodeArgs &a, uint32_t *ring, uint64_t off, uint32_t n,
@@ -845,9 +983,13 @@ __device__ void decode_range_any(const DecodeArgs &a, uint32_t *ring, uint64_t o
 
 // One wave (and one workgroup) per block; NCH x 1 KiB ring plus a guard
 // dword so linear reads of a block's last field stay inside the array.
-template <int G, uint32_t NCH, bool ARENA, bool BIG = false>
+// PAD: kFitPad bytes of LDS more (fewer waves per CU), for launches whose
+// blocks the caller declared to fit the ring.
+template <int G, uint32_t NCH, bool ARENA, bool BIG = false, bool PAD = false>
 __global__ __launch_bounds__(64) void decode_v2_kernel(DecodeArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t ring[NCH * kChunk / 4 + 4];
+    static_assert(!PAD || (!ARENA && NCH == kRingChunks), "the pad is the 8 KiB DESC ring's");
+    __shared__ __attribute__((aligned(16)))
+    uint32_t ring[NCH * kChunk / 4 + 4 + (PAD ? kFitPad / 4 : 0)];
     __shared__ uint32_t tab[ARENA ? 129 : 1];
     // a caller's launch order (largest first) is kept as given.  Large blocks
     // (the 16 KiB ring) go XCD-contiguous: 64 KiB blocks 87.9 -> 86.2 us.
@@ -864,6 +1006,11 @@ __global__ __launch_bounds__(64) void decode_v2_kernel(DecodeArgs a) {
         // inlined the register allocator needs 248 VGPRs (and spills) for
         // what each alone does in 96
         decode_block_v2<G, NCH, false, true>(a, b, ring, tab, off, n, lin);
+    } else if (lin && !BIG) {
+        // (a launch above kBigLaunch blocks keeps the general chase: for 1M
+        // blocks the straight-line path measured 844 against 755 us at 19
+        // waves per CU and 755-765 against 752-755 us with the pad)
+        decode_block_lin<G, NCH, BIG>(a, b, ring, off, n);
     } else if (lin) {
         decode_block_v2<G, NCH, true, false, BIG>(a, b, ring, tab, off, n);
     } else {
@@ -996,10 +1143,15 @@ int plan_scan(int mode, const uint32_t *d_len, uint32_t n, uint64_t *d_out, void
     return 0;
 }
 
+// fit: the caller declared every block to fit the 8 KiB ring (kFitPad).
 template <int G, bool ARENA, uint32_t NCH = kRingChunks>
-int launch_decode(const DecodeArgs &a, hipStream_t s) {
+int launch_decode(const DecodeArgs &a, hipStream_t s, bool fit = false) {
     static_assert(NCH >= 2, "a record header may straddle two ring chunks");
-    if (!ARENA && NCH == kRingChunks && a.nblk > kBigLaunch && !a.order)
+    constexpr bool kCanPad = !ARENA && NCH == kRingChunks && G != LSM_GRAMMAR_IDX;
+    const bool big = !ARENA && NCH == kRingChunks && a.nblk > kBigLaunch && !a.order;
+    if (kCanPad && fit && !big)
+        hipLaunchKernelGGL((decode_v2_kernel<G, NCH, false, false, kCanPad>), dim3(a.nblk), dim3(kWave), 0, s, a);
+    else if (big)
         hipLaunchKernelGGL((decode_v2_kernel<G, NCH, false, true>), dim3(a.nblk), dim3(kWave), 0, s, a);
     else
         hipLaunchKernelGGL((decode_v2_kernel<G, NCH, ARENA>), dim3(a.nblk), dim3(kWave), 0, s, a);
@@ -2226,9 +2378,11 @@ extern "C" int lsm_compact_records(lsm_ctx *ctx, int grammar, const uint64_t *d_
     return 0;
 }
 
-extern "C" int lsm_decode_blocks(lsm_ctx *ctx, int grammar, const uint8_t *d_in,
-                                 const uint64_t *d_blk_off, const uint32_t *d_blk_len,
-                                 uint32_t nblk, const lsm_decode_out *out, void *stream) {
+// lsm_decode_blocks; fit: the caller's bound says every block fits the 8 KiB
+// ring (launch_decode).
+static int decode_blocks_8k(lsm_ctx *ctx, int grammar, const uint8_t *d_in,
+                            const uint64_t *d_blk_off, const uint32_t *d_blk_len, uint32_t nblk,
+                            const lsm_decode_out *out, void *stream, bool fit) {
     if (!ctx || !out) return LSM_EINVAL;
     if (nblk == 0) return 0;
     if (!d_in || !d_blk_off || !d_blk_len || !out->desc || !out->nrec || !out->status)
@@ -2254,12 +2408,18 @@ extern "C" int lsm_decode_blocks(lsm_ctx *ctx, int grammar, const uint8_t *d_in,
     hipStream_t s = static_cast<hipStream_t>(stream);
     switch (grammar) {
     case LSM_GRAMMAR_V: return arena ? launch_decode<LSM_GRAMMAR_V, true>(a, s)
-                                     : launch_decode<LSM_GRAMMAR_V, false>(a, s);
+                                     : launch_decode<LSM_GRAMMAR_V, false>(a, s, fit);
     case LSM_GRAMMAR_KV: return arena ? launch_decode<LSM_GRAMMAR_KV, true>(a, s)
-                                      : launch_decode<LSM_GRAMMAR_KV, false>(a, s);
+                                      : launch_decode<LSM_GRAMMAR_KV, false>(a, s, fit);
     default: return arena ? launch_decode<LSM_GRAMMAR_IDX, true>(a, s)
                           : launch_decode<LSM_GRAMMAR_IDX, false>(a, s);
     }
+}
+
+extern "C" int lsm_decode_blocks(lsm_ctx *ctx, int grammar, const uint8_t *d_in,
+                                 const uint64_t *d_blk_off, const uint32_t *d_blk_len,
+                                 uint32_t nblk, const lsm_decode_out *out, void *stream) {
+    return decode_blocks_8k(ctx, grammar, d_in, d_blk_off, d_blk_len, nblk, out, stream, false);
 }
 
 // A caller that knows its blocks are large (max_blk_len > 32 KiB: 64 KiB data
@@ -2270,8 +2430,14 @@ extern "C" int lsm_decode_blocks_hinted(lsm_ctx *ctx, int grammar, const uint8_t
                                         const uint64_t *d_blk_off, const uint32_t *d_blk_len,
                                         uint32_t nblk, uint32_t max_blk_len,
                                         const lsm_decode_out *out, void *stream) {
+    // A bound of 3 KiB to the 8 KiB ring's size (any block start: 15 bytes of
+    // lead) declares blocks of go-lsm's own size class, which all take the
+    // straight-line path: the DESC kernel then holds kFitPad of LDS more.  A
+    // block longer than the bound still decodes correctly, only slower.
     if (max_blk_len <= 32 * 1024)
-        return lsm_decode_blocks(ctx, grammar, d_in, d_blk_off, d_blk_len, nblk, out, stream);
+        return decode_blocks_8k(ctx, grammar, d_in, d_blk_off, d_blk_len, nblk, out, stream,
+                                max_blk_len > kFitMin &&
+                                    max_blk_len + 15 <= kRingChunks * kChunk);
     if (!ctx || !out) return LSM_EINVAL;
     if (nblk == 0) return 0;
     if (!d_in || !d_blk_off || !d_blk_len || !out->desc || !out->nrec || !out->status)
