@@ -3527,6 +3527,90 @@ __global__ __launch_bounds__(kL0Threads) void level0_get_kernel(GetArgs a, int32
     }
 }
 
+// ---- the whole tree: Manager.Search (manager.go:99-133) --------------------
+//
+// Level 0 as searchFromLevel0 (:160-176), then each non-empty level 1..6 as
+// searchFromLevelWithSparseIndex + searchFromTable (:178-223); the first value
+// or error ends a key's search.  The tree is one table list, level L being
+// tables [start[L], start[L + 1]); files = lsm_level_index_build over it.
+// One thread per key does the whole of Search: the key is hashed once (at its
+// first table whose range admits it), a deeper level is searched only while
+// the key is still unanswered, and the filter bits are read from the image.
+// (The tables' MinKey prefixes staged in LDS for the sort.Search steps gave
+// 0.508 against 0.518 ms per 1M keys on the bench tree: not kept.)
+// A grouped form (every level's candidates classified and hashed once, one
+// filter test per table from LDS as lv_test_kernel, then the Gets in Manager
+// order) measured slower on the bench tree, 1.21 against 0.52 ms per 1M keys
+// (DESIGN.md sections 5 and 7): its passes are short latency-bound launches and the
+// test's one workgroup per table follows the tree's skew.
+constexpr uint32_t kSrLevels = LSM_SEARCH_LEVELS;
+constexpr uint32_t kSrMaxGrid = 8192;  // workgroups (grid-stride past them)
+
+struct SrShape {
+    uint32_t start[kSrLevels + 1];
+};
+
+__global__ __launch_bounds__(256) void search_kernel(GetArgs a, const McFile *files, SrShape S,
+                                                     int32_t *level_out, int32_t *table_out) {
+    const uint32_t n0 = S.start[1];
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.nkeys;
+         i += (uint64_t)gridDim.x * 256) {
+        const uint64_t k0 = a.koff[i], kl = a.koff[i + 1] - k0;
+        const uint8_t *kp = a.keys + k0;
+        uint32_t kw[4];
+        key_prefix(kp, kl, kw);
+        uint64_t h[4] = {0, 0, 0, 0};
+        bool hashed = false;
+        int32_t res = LSM_GET_ABSENT, tab = -1, lev = -1;
+        lsm_rec_desc v{0, 0, 0};
+        // step s: level-0 table s, then level s - n0 + 1
+        for (uint32_t s = 0; s < n0 + kSrLevels - 1 && res == LSM_GET_ABSENT; s++) {
+            const uint32_t L = s < n0 ? 0 : s - n0 + 1;
+            uint32_t f = s;
+            bool in_range;
+            if (L == 0) {  // searchFromLevel0: every table, MayContain's range check
+                const McFile &F = files[f];
+                in_range = F.ok && bound_cmp_fast(F.lo, F.lo_len, a.img + F.lo_at, kw, kl, kp) <= 0 &&
+                           bound_cmp_fast(F.hi, F.hi_len, a.img + F.hi_at, kw, kl, kp) >= 0;
+            } else {  // searchFromLevelWithSparseIndex over the level's sub-range
+                const uint32_t base = S.start[L], n = S.start[L + 1] - base;
+                if (n == 0) continue;  // manager.go:194: no candidate in an empty level
+                auto lo_at = [&](uint32_t x, uint32_t bw[4]) {
+                    for (int j = 0; j < 4; j++) bw[j] = files[base + x].lo[j];
+                };
+                const uint32_t lo = lv_search(n, lo_at, files + base, a.img, kw, kl, kp);
+                f = base + (lo ? lo - 1 : 0);  // manager.go:189-191
+                const McFile &F = files[f];
+                // MayContain: lo > 0 means MinKey <= key; then MaxKey >= key
+                in_range = lo > 0 && F.ok && bound_cmp_fast(F.hi, F.hi_len, a.img + F.hi_at, kw, kl, kp) >= 0;
+            }
+            if (!in_range) continue;
+            if (!hashed) {
+                sum256(kp, kl, h);
+                hashed = true;
+            }
+            const McFile &F = files[f];
+            // Filter.Test as each level's own entry runs it (they differ only
+            // on a corrupted m >= 2^63): lsm_level0_get's, lv_probe_kernel's.
+            // All k bits in flight: reading the first two bits first (they
+            // reject most absent keys of a 15 % full filter) measured slower,
+            // 0.588 against 0.518 ms per 1M keys
+            const uint32_t pass = L == 0 ? filter_test_any(F, h, a.img)
+                                         : filter_test<false>(F, h, nullptr, 0, a.img + F.words_at);
+            if (!pass) continue;
+            res = get_in_table(a, f, kw, kl, kp, v);
+            if (res != LSM_GET_ABSENT) {  // a value or an error: the search ends
+                tab = (int32_t)f;
+                lev = (int32_t)L;
+            }
+        }
+        a.result[i] = res;
+        a.value[i] = v;
+        table_out[i] = tab;
+        level_out[i] = lev;
+    }
+}
+
 template <int G>
 int launch_encode_blocks(const EncodeBlocksArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(encode_blocks_kernel<G>, dim3(a.nblk), dim3(kWave * kEncWaves), 0, s, a);
@@ -4288,6 +4372,69 @@ extern "C" int lsm_level0_get(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t
     if (grid > 0x7FFFFFFFull) return LSM_EINVAL;
     hipLaunchKernelGGL(level0_get_kernel, dim3((uint32_t)grid), dim3(kL0Threads), 0,
                        static_cast<hipStream_t>(stream), a, d_table);
+    LSM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The tree's shape from level_start; false when it does not start at 0 or decreases.
+static bool search_shape(const uint32_t *level_start, SrShape &S) {
+    for (uint32_t L = 0; L <= kSrLevels; L++) {
+        S.start[L] = level_start[L];
+        if (L && S.start[L] < S.start[L - 1]) return false;
+    }
+    return S.start[0] == 0;
+}
+
+// One thread per key holds its whole state: nothing per probe is kept between
+// launches, so the size depends on neither nkeys nor the tree.
+constexpr size_t kSrWsBytes = 256;
+
+extern "C" size_t lsm_search_workspace_bytes(const uint32_t *level_start, uint64_t nkeys) {
+    SrShape S{};
+    (void)nkeys;
+    if (!level_start || !search_shape(level_start, S) || S.start[kSrLevels] == 0) return 0;
+    return kSrWsBytes;
+}
+
+extern "C" int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
+                          const uint32_t *level_start, const uint64_t *d_file_off,
+                          const uint64_t *d_file_len, const lsm_sst_meta *d_meta,
+                          const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc,
+                          const int64_t *d_idx_value, const uint8_t *d_keys, const uint64_t *d_koff,
+                          uint64_t nkeys, int32_t *d_level, int32_t *d_table, int32_t *d_result,
+                          lsm_rec_desc *d_value, const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
+                          void *d_workspace, size_t ws_bytes, void *stream) {
+    if (!ctx) return LSM_EINVAL;
+    if (nkeys == 0) return 0;
+    SrShape S{};
+    if (!level_start || !search_shape(level_start, S)) return LSM_EINVAL;
+    if (!d_keys || !d_koff || !d_level || !d_table || !d_result || !d_value) return LSM_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t nfile = S.start[kSrLevels];
+    if (nfile == 0) {  // an empty tree: every key absent
+        LSM_HIP_CHECK(hipMemsetAsync(d_level, 0xFF, 4 * nkeys, s));
+        LSM_HIP_CHECK(hipMemsetAsync(d_table, 0xFF, 4 * nkeys, s));
+        LSM_HIP_CHECK(hipMemsetAsync(d_result, 0, 4 * nkeys, s));
+        LSM_HIP_CHECK(hipMemsetAsync(d_value, 0, sizeof(lsm_rec_desc) * nkeys, s));
+        return 0;
+    }
+    if (!d_img || !d_index || !d_file_off || !d_file_len || !d_meta || !d_idx_desc || !d_idx_value ||
+        !d_workspace)
+        return LSM_EINVAL;
+    if (ws_bytes < kSrWsBytes) return LSM_ESPACE;
+    GetArgs a = get_args(d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc,
+                         d_idx_value);
+    a.keys = d_keys;
+    a.koff = d_koff;
+    a.nkeys = nkeys;
+    a.result = d_result;
+    a.value = d_value;
+    const int rc = get_tree_args(a, nfile, d_tree, tree_nidx, tree_bytes);
+    if (rc) return rc;
+    const McFile *files = static_cast<const McFile *>(d_index);
+    const uint64_t g = (nkeys + 255) / 256;
+    const dim3 grid(g < kSrMaxGrid ? (uint32_t)g : kSrMaxGrid);
+    hipLaunchKernelGGL(search_kernel, grid, dim3(256), 0, s, a, files, S, d_level, d_table);
     LSM_HIP_CHECK(hipGetLastError());
     return 0;
 }

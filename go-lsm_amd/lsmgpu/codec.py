@@ -621,6 +621,66 @@ def level0_get(ctx: Context, d_img: torch.Tensor, r: SstDecode, batch: "RecordBa
     return table[:batch.n], result[:batch.n], value[:batch.n]
 
 
+SEARCH_LEVELS = 7  # LSM_SEARCH_LEVELS
+
+
+def _level_start(level_start) -> np.ndarray:
+    ls = np.ascontiguousarray(level_start, dtype=np.uint32)
+    if ls.shape != (SEARCH_LEVELS + 1,):
+        raise ValueError(f"level_start needs {SEARCH_LEVELS + 1} entries")
+    return ls
+
+
+def search_workspace(ctx: Context, level_start, nkeys: int) -> torch.Tensor:
+    ls = _level_start(level_start)
+    n = int(ctx.lib.lsm_search_workspace_bytes(ls.ctypes.data, nkeys))
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=ctx.torch_device)
+
+
+def search_into(ctx: Context, d_img: torch.Tensor, r: SstDecode, level_start, batch: "RecordBatch",
+                index: torch.Tensor, level: torch.Tensor, table: torch.Tensor, result: torch.Tensor,
+                value: torch.Tensor, tree: Optional[SeekTree] = None,
+                ws: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lsm_search: Manager.Search (manager.go:99-133) of every key of `batch`
+    over the whole tree decoded into r -- tables [level_start[L],
+    level_start[L + 1]) are level L, level 0 newest first, the deeper levels in
+    sparse-index order.  index = level_index over r, tree = level_get_tree
+    over r (or None).  level / table int32 per key (the answering table's level
+    and its index in r, -1 when absent), result / value as level_get_into."""
+    ls = _level_start(level_start)
+    if int(ls[-1]) != r.nfile:
+        raise ValueError(f"level_start ends at {int(ls[-1])}, the tree holds {r.nfile} tables")
+    if ws is None:
+        ws = search_workspace(ctx, ls, batch.n)
+    nf = r.nfile
+    _lib.check(ctx.lib.lsm_search(
+        ctx.handle, _ptr(d_img) if nf else None, _ptr(index) if nf else None, ls.ctypes.data,
+        _ptr(r.d_file_off) if nf else None, _ptr(r.d_file_len) if nf else None, _ptr(r.meta) if nf else None,
+        None, _ptr(r.idx_desc) if nf else None, _ptr(r.idx_value) if nf else None,
+        _ptr(batch.keys), _ptr(batch.koff), batch.n, _ptr(level), _ptr(table), _ptr(result), _ptr(value),
+        _ptr(tree.data) if tree is not None else None, tree.max_nidx if tree is not None else 0,
+        tree.data.numel() if tree is not None else 0, _ptr(ws), ws.numel(), _stream_handle(stream)),
+        "lsm_search")
+
+
+def search(ctx: Context, d_img: torch.Tensor, r: SstDecode, level_start, batch: "RecordBatch",
+           index: Optional[torch.Tensor] = None, tree: Optional[SeekTree] = None, stream=None):
+    """-> (level int32[nkeys], table int32[nkeys], result int32[nkeys],
+    value int32[nkeys, 4]) on the device."""
+    dev = ctx.torch_device
+    n = max(batch.n, 1)
+    level = torch.empty(n, dtype=torch.int32, device=dev)
+    table = torch.empty(n, dtype=torch.int32, device=dev)
+    result = torch.empty(n, dtype=torch.int32, device=dev)
+    value = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if index is None:
+        index = level_index(ctx, d_img, r, stream=stream)
+    if batch.n:
+        search_into(ctx, d_img, r, level_start, batch, index, level, table, result, value, tree=tree,
+                    stream=stream)
+    return level[:batch.n], table[:batch.n], result[:batch.n], value[:batch.n]
+
+
 # ---- encode -----------------------------------------------------------------
 
 @dataclass

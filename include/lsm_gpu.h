@@ -49,7 +49,10 @@ extern "C" {
  * Seek tree's size; lsm_level0_get (searchFromLevel0 over every table);
  * lsm_level_search_get (a level's search and Get in one call);
  * lsm_goheap_pop_order_host reports its phases, lsm_goheap_replays;
- * lsm_build_flags. */
+ * lsm_build_flags.
+ * Added within v7 (backward compatible, the version stays 7; a binding finds
+ * them by symbol lookup): lsm_search and lsm_search_workspace_bytes
+ * (Manager.Search over a whole tree in one call). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -423,6 +426,50 @@ int lsm_level0_get(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_of
                    const int64_t *d_idx_value, const uint8_t *d_keys, const uint64_t *d_koff,
                    uint64_t nkeys, int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value,
                    const void *d_tree, uint32_t tree_nidx, size_t tree_bytes, void *stream);
+
+/* Batched Manager.Search (sstable/manager.go:99-133) over a whole tree in one
+ * asynchronous call (added within ABI 7): what database.Get reaches the
+ * SSTables through.  The tree is one table list of nfile = level_start[7]
+ * images in one d_img, decoded by one lsm_decode_sst; tables
+ * [level_start[L], level_start[L + 1]) are level L (level_start is a HOST
+ * array of LSM_SEARCH_LEVELS + 1 entries, level_start[0] = 0, non-decreasing
+ * or the call returns LSM_EINVAL; go-lsm's 2^(L+1) cap per level is not
+ * enforced).  Level 0 is in the Manager's order, newest first, as for
+ * lsm_level0_get; each level >= 1 is in sparse-index order, as for
+ * lsm_level_may_contain.  d_index is lsm_level_index_build over the whole
+ * list, d_tree lsm_level_get_tree_build over the whole list (or NULL); both
+ * work per table.  Per key i: level 0 as searchFromLevel0 (:160-176), then
+ * each non-empty level 1..6 as searchFromLevelWithSparseIndex +
+ * searchFromTable (:178-223); the first result other than LSM_GET_ABSENT -- a
+ * value or any error code -- ends that key's search.  A found value that is
+ * empty or the tombstone bytes (kv.go:29-31) is a found value: Search and
+ * database.Get do not interpret it.  waitForCompactionIfNeeded is host locking
+ * and stays with the binding.  Corrupted tables answer as in lsm_level0_get
+ * (level 0) and lsm_level_may_contain (levels >= 1).
+ * d_result[i] / d_value[i] as lsm_level_get; d_table[i] = the answering
+ * table's index in the tree's list and d_level[i] its level, both -1 when the
+ * key is absent.  nkeys == 0 returns 0; an empty tree answers every key
+ * absent; LSM_ESPACE for a workspace or a tree buffer that is too small.
+ * One launch whatever the tree's depth and nkeys: one thread per key runs the
+ * whole of Search -- the key hashed once, a deeper level searched only while
+ * the key is unanswered, so no work is spent on keys an earlier level
+ * answered.  No host round trip, no read-back (the call can be captured in a
+ * graph) and no device allocation.
+ * Workspace: lsm_search_workspace_bytes = 256 for every non-empty tree and
+ * every nkeys (0 for an empty tree, or a level_start that does not start at 0
+ * or decreases): a thread holds its key's whole state, nothing per probe is
+ * kept between launches.  The buffer is reserved for a grouped form of the
+ * search; a smaller one returns LSM_ESPACE. */
+#define LSM_SEARCH_LEVELS 7 /* minSSTableLevel .. maxSSTableLevel, manager.go:21-22 */
+size_t lsm_search_workspace_bytes(const uint32_t *level_start, uint64_t nkeys);
+int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
+               const uint32_t *level_start, /* HOST, LSM_SEARCH_LEVELS + 1 entries */
+               const uint64_t *d_file_off, const uint64_t *d_file_len, const lsm_sst_meta *d_meta,
+               const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value,
+               const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys,
+               int32_t *d_level, int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value,
+               const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
+               void *d_workspace, size_t ws_bytes, void *stream);
 
 /* The Seek tree of a level for lsm_level_get, built once when the level is
  * loaded (the Manager keeps each table's decoded IndexBlock in memory,
