@@ -1,0 +1,482 @@
+// memtable.hip — the memtable's result on the device (lsm_memtable_order).
+//
+// A go-lsm memtable is a skiplist in which a later Add of a key replaces the
+// earlier pair (memtable/skiplist/skiplist.go:83-118); MemTable.Insert appends
+// to the WAL before AddPair (memtable.go:68-78).  Its contents are therefore
+// "the last record of each key of its WAL, in key order": a segmented sort
+// with last-writer-wins over lsm_wal_replay's descriptors.
+//
+// Per log: tiles of kTile records are sorted in LDS (bitonic, on each key's
+// first 16 bytes; the rest from the log on a tie), log2(tiles) rank-merge
+// passes join them over ping-pong buffers of (16 key bytes, slot), and
+// the finish keeps the last element of each run of equal keys, applies
+// IMemTable.RangeScan's cut and compacts the survivors' slots across logs.
+// The order is total -- (key, slot) -- so no pass needs to be stable.
+#include "common.h"
+
+namespace {
+
+using namespace lsm;
+
+constexpr uint32_t kTile = 1024;     // records per LDS tile (LSM_MEMTABLE_TILE)
+constexpr uint32_t kThreads = 256;   // every other kernel's workgroup
+// the tile sort's workgroup: one compare-exchange per thread and stage (its 55
+// barrier-separated stages are latency, not throughput)
+constexpr uint32_t kSortThreads = kTile / 2;
+constexpr uint32_t kPad = 0xFFFFFFFFu;  // slot of a tile's padding element
+constexpr uint32_t kTombBit = 0x80000000u;
+constexpr uint64_t kOverflowBit = 1ull << 63;
+
+struct Logs {
+    const uint8_t *bytes;
+    const lsm_rec_desc *desc;
+    const uint64_t *rec_base;  // or NULL: base = log_off[w] / 8
+    const uint64_t *log_off;
+    const uint32_t *nrec;
+    const int32_t *status;
+    uint32_t nlog;
+    uint32_t nslot;
+    uint32_t maxrec;
+};
+
+// The records of log w this call orders: [*base, *base + n) of desc.  A log
+// whose replay failed, or whose records do not fit maxrec / nslot, has none.
+__device__ __forceinline__ uint32_t log_span(const Logs &L, uint32_t w, uint32_t *base, bool *overflow) {
+    const uint64_t b = L.rec_base ? L.rec_base[w] : L.log_off[w] / 8;
+    const uint32_t n = L.nrec[w];
+    const bool failed = L.status[w] != 0;
+    const bool over = !failed && (n > L.maxrec || b > L.nslot || n > L.nslot - b);
+    if (overflow) *overflow = over;
+    *base = (uint32_t)b;
+    return failed || over ? 0 : n;
+}
+
+__device__ __forceinline__ uint64_t load8(const uint8_t *p) {
+    uint64_t v;
+    __builtin_memcpy(&v, p, 8);
+    return v;
+}
+
+// A key's first 16 bytes as two big-endian integers, zero padded: compared as
+// (hi, lo) they order keys that differ there; equal, with either key at most
+// 16 bytes long, the shorter key is a prefix of the other and sorts first.
+struct alignas(16) Key16 {
+    uint64_t hi, lo;
+};
+
+// 8 key bytes from `at` as a big-endian integer, zero padded past the key.
+// Reads 8 bytes whatever the key's length (the input slack covers them).
+__device__ __forceinline__ uint64_t key_word(const uint8_t *key, uint32_t klen, uint32_t at) {
+    if (klen <= at) return 0;
+    uint64_t v = __builtin_bswap64(load8(key + at));
+    const uint32_t left = klen - at;
+    if (left < 8) v &= ~0ull << (8 * (8 - left));
+    return v;
+}
+
+__device__ __forceinline__ Key16 key16_of(const Logs &L, uint32_t slot) {
+    const lsm_rec_desc d = L.desc[slot];
+    const uint8_t *key = L.bytes + d.rec_off + 4;
+    return Key16{key_word(key, d.key_len, 0), key_word(key, d.key_len, 8)};
+}
+
+// Keys a and b (slots) whose first 16 bytes are equal: <0, 0, >0 in Go string order.
+__device__ int key_cmp_tail(const Logs &L, uint32_t a, uint32_t b) {
+    const lsm_rec_desc da = L.desc[a], db = L.desc[b];
+    const uint32_t la = da.key_len, lb = db.key_len;
+    const uint32_t lm = la < lb ? la : lb;
+    if (lm > 16) {
+        const uint8_t *pa = L.bytes + da.rec_off + 4, *pb = L.bytes + db.rec_off + 4;
+        for (uint32_t j = 16; j < lm; j += 8) {
+            const uint64_t x = key_word(pa, lm, j), y = key_word(pb, lm, j);
+            if (x != y) return x < y ? -1 : 1;
+        }
+    }
+    return la == lb ? 0 : (la < lb ? -1 : 1);
+}
+
+// (key, slot) order; a padding element sorts last.
+__device__ __forceinline__ bool item_less(const Logs &L, Key16 ka, uint32_t a, Key16 kb, uint32_t b) {
+    if (a == kPad) return false;
+    if (b == kPad) return true;
+    if (ka.hi != kb.hi) return ka.hi < kb.hi;
+    if (ka.lo != kb.lo) return ka.lo < kb.lo;
+    const int c = key_cmp_tail(L, a, b);
+    return c ? c < 0 : a < b;
+}
+
+// kv.DeletedValue (kv/kv.go:29-31), 13 bytes; IsDeleted compares the whole value.
+__device__ bool is_tombstone(const Logs &L, uint32_t slot) {
+    const lsm_rec_desc d = L.desc[slot];
+    if (d.val_len != 13) return false;
+    const uint8_t t[13] = {0xEF, 0xBD, 0x9E, 'D', 'E', 'L', 'E', 'T', 'E', 'D', 0xEF, 0xBD, 0x9E};
+    const uint8_t *v = L.bytes + d.rec_off + 8 + d.key_len;
+    bool eq = true;
+    for (int i = 0; i < 13; i++) eq &= v[i] == t[i];
+    return eq;
+}
+
+// ---- tile sort: one workgroup per tile of one log --------------------------
+
+__global__ __launch_bounds__(kSortThreads) void mt_tile_sort(Logs L, Key16 *key_out, uint32_t *pos_out) {
+    __shared__ uint64_t s_hi[kTile], s_lo[kTile];
+    __shared__ uint32_t s_pos[kTile];
+    const uint32_t w = blockIdx.y;
+    uint32_t base;
+    const uint32_t n = log_span(L, w, &base, nullptr);
+    const uint32_t t0 = blockIdx.x * kTile;
+    if (t0 >= n) return;
+    const uint32_t cnt = n - t0 < kTile ? n - t0 : kTile;
+    for (uint32_t i = threadIdx.x; i < kTile; i += kSortThreads) {
+        if (i < cnt) {
+            const uint32_t slot = base + t0 + i;
+            const Key16 k = key16_of(L, slot);
+            s_hi[i] = k.hi;
+            s_lo[i] = k.lo;
+            s_pos[i] = slot;
+        } else {
+            s_hi[i] = s_lo[i] = ~0ull;
+            s_pos[i] = kPad;
+        }
+    }
+    __syncthreads();
+    // the smallest power of two that holds the tile's records
+    uint32_t m = 2;
+    while (m < cnt) m <<= 1;
+    for (uint32_t k = 2; k <= m; k <<= 1) {
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < m / 2; t += kSortThreads) {
+                const uint32_t lo = 2 * t - (t & (j - 1)), hi = lo + j;
+                const bool up = (lo & k) == 0;
+                const Key16 ka{s_hi[lo], s_lo[lo]}, kb{s_hi[hi], s_lo[hi]};
+                const uint32_t a = s_pos[lo], b = s_pos[hi];
+                if (item_less(L, kb, b, ka, a) == up) {
+                    s_hi[lo] = kb.hi;
+                    s_lo[lo] = kb.lo;
+                    s_pos[lo] = b;
+                    s_hi[hi] = ka.hi;
+                    s_lo[hi] = ka.lo;
+                    s_pos[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (uint32_t i = threadIdx.x; i < cnt; i += kSortThreads) {  // the keys travel with the indices
+        key_out[base + t0 + i] = Key16{s_hi[i], s_lo[i]};
+        pos_out[base + t0 + i] = s_pos[i];
+    }
+}
+
+// ---- merge pass: runs of `run` elements joined in pairs --------------------
+
+// Each element finds its place by counting the partner run's smaller
+// elements (a bisection; the order is total, so the places are distinct).  A
+// run without a partner is copied.
+__global__ __launch_bounds__(kThreads) void mt_merge_pass(Logs L, uint32_t run, const Key16 *key_in,
+                                                         const uint32_t *pos_in, Key16 *key_out,
+                                                         uint32_t *pos_out) {
+    const uint32_t w = blockIdx.y;
+    uint32_t base;
+    const uint32_t n = log_span(L, w, &base, nullptr);
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const Key16 ka = key_in[base + i];
+    const uint32_t a = pos_in[base + i];
+    const uint32_t r = i / run;
+    const uint64_t other = (uint64_t)(r ^ 1) * run;  // the partner run's start
+    uint32_t cnt = 0;
+    if (other < n) {
+        const uint32_t o0 = (uint32_t)other;
+        const uint32_t olen = n - o0 < run ? n - o0 : run;
+        uint32_t lo = 0, hi = olen;
+        while (lo < hi) {  // one 16-byte gather per step; the slot only when the 16 bytes tie
+            const uint32_t mid = (lo + hi) >> 1;
+            const Key16 kb = key_in[base + o0 + mid];
+            bool less;
+            if (kb.hi != ka.hi) less = kb.hi < ka.hi;
+            else if (kb.lo != ka.lo) less = kb.lo < ka.lo;
+            else less = item_less(L, kb, pos_in[base + o0 + mid], ka, a);
+            if (less) lo = mid + 1;
+            else hi = mid;
+        }
+        cnt = lo;
+    }
+    const uint32_t pair0 = (r & ~1u) * run;  // < n
+    const uint32_t dst = base + pair0 + (i - r * run) + cnt;
+    key_out[dst] = ka;
+    pos_out[dst] = a;
+}
+
+// ---- finish -----------------------------------------------------------------
+
+// The least of a workgroup's candidate ranks (kPad: none) -> blk[b].  The
+// candidates of all workgroups of a log are reduced by mt_min_blocks: one
+// atomic per wave on the log's word serialised every wave of the log.
+__device__ __forceinline__ void block_min_out(uint32_t cand, uint32_t *s_min, uint32_t *out) {
+    if (threadIdx.x == 0) *s_min = kPad;
+    __syncthreads();
+    const uint64_t any = __ballot(cand != kPad);
+    // ranks rise with the lane: the wave's first candidate is its least
+    if (any && lane_id() == (uint32_t)__ffsll((long long)any) - 1) atomicMin(s_min, cand);
+    __syncthreads();
+    if (threadIdx.x == 0) *out = *s_min;
+}
+
+// flag[base + i] = 1 when sorted element i is the last of its key (the
+// memtable's node), | kTombBit when its value is the tombstone; the
+// workgroup's survivor count goes to blkcnt.
+__global__ __launch_bounds__(kThreads) void mt_flag(Logs L, const Key16 *key, const uint32_t *pos,
+                                                   uint32_t *flag, uint32_t *blkcnt, uint32_t nblk) {
+    __shared__ uint32_t s_cnt;
+    const uint32_t w = blockIdx.y;
+    uint32_t base;
+    const uint32_t n = log_span(L, w, &base, nullptr);
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    uint32_t f = 0;
+    if (i < n) {
+        const uint32_t a = pos[base + i];
+        bool last = i + 1 == n;
+        if (!last) {
+            const uint32_t b = pos[base + i + 1];
+            const Key16 ka = key[base + i], kb = key[base + i + 1];
+            last = ka.hi != kb.hi || ka.lo != kb.lo || key_cmp_tail(L, a, b) != 0;
+        }
+        if (last) f = 1 | (is_tombstone(L, a) ? kTombBit : 0);
+        flag[base + i] = f;
+    }
+    const uint64_t bal = __ballot(f != 0);
+    if (lane_id() == 0 && bal) atomicAdd(&s_cnt, (uint32_t)__popcll(bal));
+    __syncthreads();
+    if (threadIdx.x == 0) blkcnt[(size_t)w * nblk + blockIdx.x] = s_cnt;
+}
+
+// One wave per log: blkcnt -> exclusive offsets, the log's node count; lead
+// and cut start at that count (RangeScan's window [lead, cut) is then empty
+// until mt_rank / mt_cut lower them).
+__global__ __launch_bounds__(kWave) void mt_scan_blocks(uint32_t *blkcnt, uint32_t nblk, uint32_t *total,
+                                                       uint32_t *lead, uint32_t *cut) {
+    const uint32_t w = blockIdx.x;
+    uint32_t *c = blkcnt + (size_t)w * nblk;
+    uint32_t carry = 0;
+    for (uint32_t b0 = 0; b0 < nblk; b0 += kWave) {
+        const uint32_t b = b0 + lane_id();
+        const uint32_t v = b < nblk ? c[b] : 0;
+        uint32_t sum;
+        const uint32_t ex = wave_excl_scan(v, &sum);
+        if (b < nblk) c[b] = carry + ex;
+        carry += sum;
+    }
+    if (lane_id() == 0) {
+        total[w] = carry;
+        lead[w] = carry;
+        cut[w] = carry;
+    }
+}
+
+// flag -> the node's rank in its log (| kTombBit), kPad for a replaced record;
+// RANGESCAN: the workgroup's first node that is no tombstone goes to its
+// blkoff word; the least of a log's is lead (SeekToFirst, iterator.go:27-33).
+__global__ __launch_bounds__(kThreads) void mt_rank(Logs L, uint32_t *flag, uint32_t *blkoff, uint32_t nblk,
+                                                   int scan) {
+    __shared__ uint32_t s_wave[kThreads / kWave];
+    __shared__ uint32_t s_min;
+    const uint32_t w = blockIdx.y;
+    uint32_t base;
+    const uint32_t n = log_span(L, w, &base, nullptr);
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t f = i < n ? flag[base + i] : 0;
+    const uint64_t bal = __ballot(f != 0);
+    const uint32_t wv = threadIdx.x / kWave;
+    if (lane_id() == 0) s_wave[wv] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = blkoff[(size_t)w * nblk + blockIdx.x];
+    for (uint32_t k = 0; k < wv; k++) before += s_wave[k];
+    const uint32_t r = before + mbcnt(bal);
+    if (i < n) flag[base + i] = f ? r | (f & kTombBit) : kPad;
+    if (scan == LSM_MEMTABLE_RANGESCAN)  // the offset was read above: the word now holds the candidate
+        block_min_out(f && !(f & kTombBit) ? r : kPad, &s_min, &blkoff[(size_t)w * nblk + blockIdx.x]);
+}
+
+// RANGESCAN: the first tombstone past lead ends the scan (Valid,
+// iterator.go:68-70, ends the loop of imemtable.go:46-53 there): the
+// workgroup's candidate, reduced to cut by mt_min_blocks.
+__global__ __launch_bounds__(kThreads) void mt_cut(Logs L, const uint32_t *rank, const uint32_t *lead,
+                                                  uint32_t *blk, uint32_t nblk) {
+    __shared__ uint32_t s_min;
+    const uint32_t w = blockIdx.y;
+    uint32_t base;
+    const uint32_t n = log_span(L, w, &base, nullptr);
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t f = i < n ? rank[base + i] : kPad;
+    const uint32_t r = f & ~kTombBit;
+    block_min_out(f != kPad && (f & kTombBit) && r > lead[w] ? r : kPad, &s_min,
+                  &blk[(size_t)w * nblk + blockIdx.x]);
+}
+
+// One wave per log: dst[w] = the least candidate of the log's workgroups, when
+// there is one (dst starts at the log's node count).
+__global__ __launch_bounds__(kWave) void mt_min_blocks(const uint32_t *blk, uint32_t nblk, uint32_t *dst) {
+    const uint32_t w = blockIdx.x;
+    uint32_t m = kPad;
+    for (uint32_t b = lane_id(); b < nblk; b += kWave) {
+        const uint32_t v = blk[(size_t)w * nblk + b];
+        m = v < m ? v : m;
+    }
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const uint32_t v = (uint32_t)__shfl_xor((int)m, o);
+        m = v < m ? v : m;
+    }
+    if (lane_id() == 0 && m != kPad) dst[w] = m;
+}
+
+// One wave: each log's delivered count -> file_start (exclusive scan) and the
+// three counts.  ALL: lead = 0 and cut = the node count.
+__global__ __launch_bounds__(kWave) void mt_scan_logs(Logs L, int scan, const uint32_t *total, uint32_t *lead,
+                                                     uint32_t *cut, uint64_t *file_start, uint64_t *counts) {
+    uint64_t carry = 0;
+    uint32_t nonempty = 0, most = 0, over = 0;
+    for (uint32_t w0 = 0; w0 < L.nlog; w0 += kWave) {
+        const uint32_t w = w0 + lane_id();
+        uint64_t v = 0;
+        if (w < L.nlog) {
+            uint32_t base;
+            bool o;
+            log_span(L, w, &base, &o);
+            over |= o;
+            if (scan == LSM_MEMTABLE_ALL) {
+                lead[w] = 0;
+                cut[w] = total[w];
+            }
+            v = cut[w] - lead[w];  // lead <= cut <= total
+            nonempty += v != 0;
+            most = v > most ? (uint32_t)v : most;
+        }
+        uint64_t sum;
+        const uint64_t ex = wave_excl_scan64(v, &sum);
+        if (w < L.nlog) file_start[w] = carry + ex;
+        carry += sum;
+    }
+    __shared__ uint32_t s_ne[kWave], s_most[kWave], s_over[kWave];
+    s_ne[lane_id()] = nonempty;
+    s_most[lane_id()] = most;
+    s_over[lane_id()] = over;
+    __syncthreads();
+    if (lane_id() == 0) {
+        uint32_t ne = 0, mo = 0, ov = 0;
+        for (int k = 0; k < kWave; k++) {
+            ne += s_ne[k];
+            mo = s_most[k] > mo ? s_most[k] : mo;
+            ov |= s_over[k];
+        }
+        file_start[L.nlog] = carry;
+        counts[0] = carry;
+        counts[1] = ne;
+        counts[2] = (uint64_t)mo | (ov ? kOverflowBit : 0);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void mt_emit(Logs L, const uint32_t *pos, const uint32_t *rank,
+                                                   const uint32_t *lead, const uint32_t *cut,
+                                                   const uint64_t *file_start, uint32_t *idx) {
+    const uint32_t w = blockIdx.y;
+    uint32_t base;
+    const uint32_t n = log_span(L, w, &base, nullptr);
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = rank[base + i];
+    if (f == kPad) return;
+    const uint32_t r = f & ~kTombBit, l = lead[w];
+    if (r < l || r >= cut[w]) return;
+    idx[file_start[w] + (r - l)] = pos[base + i];
+}
+
+struct Ws {
+    Key16 *key[2];
+    uint32_t *pos[2];
+    uint32_t *blkcnt, *total, *lead, *cut;
+};
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+uint32_t blocks_per_log(uint32_t maxrec) { return (maxrec + kThreads - 1) / kThreads; }
+
+size_t ws_layout(uint8_t *p, uint32_t nlog, uint64_t nslot, uint32_t maxrec, Ws *w) {
+    const size_t s8 = align256(16 * nslot), s4 = align256(4 * nslot);  // s8: one Key16 buffer
+    const size_t sb = align256(4 * (size_t)nlog * blocks_per_log(maxrec)), sl = align256(4 * (size_t)nlog);
+    if (w) {
+        w->key[0] = reinterpret_cast<Key16 *>(p);
+        w->key[1] = reinterpret_cast<Key16 *>(p + s8);
+        w->pos[0] = reinterpret_cast<uint32_t *>(p + 2 * s8);
+        w->pos[1] = reinterpret_cast<uint32_t *>(p + 2 * s8 + s4);
+        w->blkcnt = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4);
+        w->total = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4 + sb);
+        w->lead = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4 + sb + sl);
+        w->cut = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4 + sb + 2 * sl);
+    }
+    return 2 * s8 + 2 * s4 + sb + 3 * sl;
+}
+
+}  // namespace
+
+extern "C" size_t lsm_memtable_order_workspace_bytes(uint32_t nlog, uint64_t nslot,
+                                                     uint32_t max_log_records) {
+    if (nlog == 0) return 0;
+    return ws_layout(nullptr, nlog, nslot, max_log_records, nullptr);
+}
+
+extern "C" int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                                  const uint64_t *d_rec_base, const uint64_t *d_log_off,
+                                  const uint32_t *d_nrec, const int32_t *d_status, uint32_t nlog,
+                                  uint64_t nslot, uint32_t max_log_records, int scan, uint32_t *d_idx,
+                                  uint64_t *d_file_start, uint64_t *d_counts, void *d_ws,
+                                  size_t ws_bytes, void *stream) {
+    if (!ctx || (scan != LSM_MEMTABLE_ALL && scan != LSM_MEMTABLE_RANGESCAN)) return LSM_EINVAL;
+    if (nlog == 0) return 0;
+    // slots are u32 indices (d_idx); a rank keeps its top bit for the tombstone
+    if (nslot >= 0xFFFFFFFFull || max_log_records >= 0x80000000u || nlog > 65535) return LSM_EINVAL;
+    if (!d_nrec || !d_status || !d_file_start || !d_counts || (!d_rec_base && !d_log_off))
+        return LSM_EINVAL;
+    if (nslot && max_log_records && (!d_bytes || !d_desc || !d_idx)) return LSM_EINVAL;
+    if (!d_ws || ws_bytes < lsm_memtable_order_workspace_bytes(nlog, nslot, max_log_records))
+        return LSM_ESPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    Ws ws;
+    ws_layout(static_cast<uint8_t *>(d_ws), nlog, nslot, max_log_records, &ws);
+    // with no slot or no admitted record every log is empty (or overflows)
+    const Logs L{d_bytes, d_desc, d_rec_base, d_log_off, d_nrec, d_status, nlog, (uint32_t)nslot,
+                 nslot ? max_log_records : 0};
+    const uint32_t nblk = blocks_per_log(max_log_records);
+    const uint32_t ntile = (L.maxrec + kTile - 1) / kTile;
+    int cur = 0;
+    if (ntile) {
+        hipLaunchKernelGGL(mt_tile_sort, dim3(ntile, nlog), dim3(kSortThreads), 0, s, L, ws.key[0], ws.pos[0]);
+        for (uint64_t run = kTile; run < L.maxrec; run *= 2) {
+            hipLaunchKernelGGL(mt_merge_pass, dim3(nblk, nlog), dim3(kThreads), 0, s, L, (uint32_t)run,
+                               ws.key[cur], ws.pos[cur], ws.key[cur ^ 1], ws.pos[cur ^ 1]);
+            cur ^= 1;
+        }
+    }
+    uint32_t *flag = ws.pos[cur ^ 1];  // the idle index buffer: flags, then ranks
+    if (nblk)
+        hipLaunchKernelGGL(mt_flag, dim3(nblk, nlog), dim3(kThreads), 0, s, L, ws.key[cur], ws.pos[cur], flag,
+                           ws.blkcnt, nblk);
+    hipLaunchKernelGGL(mt_scan_blocks, dim3(nlog), dim3(kWave), 0, s, ws.blkcnt, nblk, ws.total, ws.lead,
+                       ws.cut);
+    if (nblk) {
+        hipLaunchKernelGGL(mt_rank, dim3(nblk, nlog), dim3(kThreads), 0, s, L, flag, ws.blkcnt, nblk, scan);
+        if (scan == LSM_MEMTABLE_RANGESCAN) {
+            hipLaunchKernelGGL(mt_min_blocks, dim3(nlog), dim3(kWave), 0, s, ws.blkcnt, nblk, ws.lead);
+            hipLaunchKernelGGL(mt_cut, dim3(nblk, nlog), dim3(kThreads), 0, s, L, flag, ws.lead, ws.blkcnt, nblk);
+            hipLaunchKernelGGL(mt_min_blocks, dim3(nlog), dim3(kWave), 0, s, ws.blkcnt, nblk, ws.cut);
+        }
+    }
+    hipLaunchKernelGGL(mt_scan_logs, dim3(1), dim3(kWave), 0, s, L, scan, ws.total, ws.lead, ws.cut,
+                       d_file_start, d_counts);
+    if (nblk)
+        hipLaunchKernelGGL(mt_emit, dim3(nblk, nlog), dim3(kThreads), 0, s, L, ws.pos[cur], flag, ws.lead,
+                           ws.cut, d_file_start, d_idx);
+    LSM_HIP_CHECK(hipGetLastError());
+    return 0;
+}

@@ -940,5 +940,114 @@ std::vector<SSTable> CompactAndMergeKVs(const std::vector<kv::KeyValuePair> &kvs
     return results;
 }
 
+std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int scan,
+                                         std::vector<int32_t> *status, uint64_t m, uint64_t k) {
+    const size_t nlog = wals.size();
+    std::vector<Bytes> out(nlog);
+    if (status) status->assign(nlog, 0);
+    if (nlog == 0) return out;  // nothing to flush: no device call
+    Device &d = Device::ThisThread();
+    std::vector<uint64_t> off(nlog);
+    std::vector<uint32_t> len(nlog);
+    size_t total = 0, max_len = 0;
+    for (size_t w = 0; w < nlog; w++) {
+        off[w] = total;
+        len[w] = (uint32_t)wals[w].size();
+        max_len = std::max(max_len, wals[w].size());
+        total += (wals[w].size() + 15) & ~(size_t)15;
+    }
+    uint8_t *h = (uint8_t *)d.Host(0, pad16(total));
+    std::memset(h, 0, pad16(total));
+    for (size_t w = 0; w < nlog; w++)
+        if (!wals[w].empty()) std::memcpy(h + off[w], wals[w].data(), wals[w].size());
+    // wal.Recover of every log (offset-addressed: log w's records at slot off[w] / 8)
+    const uint64_t nslot = total / 8 + 1;
+    const uint32_t maxrec = (uint32_t)lsm_max_records(LSM_GRAMMAR_KV, max_len);
+    void *d_wal = d.Dev(0, pad16(total));
+    void *d_off = d.Dev(1, nlog * 8);
+    void *d_len = d.Dev(2, nlog * 4);
+    void *d_desc = d.Dev(3, nslot * sizeof(lsm_rec_desc));
+    void *d_nrec = d.Dev(4, nlog * 4);
+    void *d_st = d.Dev(5, nlog * 4);
+    const size_t wws = lsm_wal_replay_workspace_bytes((uint32_t)nlog, (uint32_t)max_len);
+    void *d_wws = d.Dev(6, wws);
+    d.H2D(d_wal, h, pad16(total));
+    d.H2D(d_off, off.data(), nlog * 8);
+    d.H2D(d_len, len.data(), nlog * 4);
+    lsm_decode_out o{};
+    o.desc = (lsm_rec_desc *)d_desc;
+    o.nrec = (uint32_t *)d_nrec;
+    o.status = (int32_t *)d_st;
+    check(lsm_wal_replay(d.ctx(), (const uint8_t *)d_wal, (const uint64_t *)d_off, (const uint32_t *)d_len,
+                         (uint32_t)nlog, (uint32_t)max_len, &o, d_wws, wws, d.stream()),
+          "lsm_wal_replay");
+    // the memtables: each log's last record per key, in key order
+    void *d_idx = d.Dev(7, nslot * 4);
+    uint64_t *d_fsc = (uint64_t *)d.Dev(8, (nlog + 1 + 3) * 8);  // file starts, then the counts
+    const size_t ows = lsm_memtable_order_workspace_bytes((uint32_t)nlog, nslot, maxrec);
+    void *d_ows = d.Dev(9, ows);
+    check(lsm_memtable_order(d.ctx(), (const uint8_t *)d_wal, (const lsm_rec_desc *)d_desc, nullptr,
+                             (const uint64_t *)d_off, (const uint32_t *)d_nrec, (const int32_t *)d_st,
+                             (uint32_t)nlog, nslot, maxrec, scan, (uint32_t *)d_idx, d_fsc,
+                             d_fsc + nlog + 1, d_ows, ows, d.stream()),
+          "lsm_memtable_order");
+    // their keys packed; the values stay in the WAL bytes
+    const uint64_t nout_max = std::min<uint64_t>(nslot, total / 8);
+    void *d_keys = d.Dev(10, pad16(total));
+    void *d_koff = d.Dev(11, (nout_max + 1) * 8);
+    void *d_voff = d.Dev(12, (nout_max + 1) * 8);
+    const size_t gws = lsm_gather_kvs_workspace_bytes(nout_max);
+    void *d_gws = d.Dev(13, gws);
+    check(lsm_gather_kvs_dev(d.ctx(), (const uint8_t *)d_wal, (const lsm_rec_desc *)d_desc, nullptr,
+                             (const uint32_t *)d_idx, d_fsc + nlog + 1, nout_max, (uint8_t *)d_keys,
+                             (uint64_t *)d_koff, nullptr, (uint64_t *)d_voff, d_gws, gws, d.stream()),
+          "lsm_gather_kvs_dev");
+    std::vector<uint64_t> fsc(nlog + 1 + 3);
+    std::vector<int32_t> st(nlog);
+    d.D2H(fsc.data(), d_fsc, fsc.size() * 8);  // the one read-back before the build
+    d.D2H(st.data(), d_st, nlog * 4);
+    d.Sync();
+    if (status) *status = st;
+    // one file per non-empty memtable (an empty one has no Header to encode)
+    std::vector<uint64_t> fs;
+    std::vector<size_t> log_of;
+    for (size_t w = 0; w < nlog; w++)
+        if (fsc[w + 1] > fsc[w]) {
+            fs.push_back(fsc[w]);
+            log_of.push_back(w);
+        }
+    const uint32_t nf = (uint32_t)fs.size();
+    if (nf == 0) return out;
+    fs.push_back(fsc[nlog]);
+    const uint32_t maxr = (uint32_t)(fsc[nlog + 3] & ~LSM_MEMTABLE_OVERFLOW);
+    void *d_fs = d.Dev(14, fs.size() * 8);
+    void *d_sz = d.Dev(15, nf * 8);
+    void *d_fo = d.Dev(16, (nf + 1) * 8);
+    d.H2D(d_fs, fs.data(), fs.size() * 8);
+    check(lsm_sst_layout(d.ctx(), (const uint64_t *)d_koff, (const uint64_t *)d_voff, (const uint64_t *)d_fs,
+                         nf, m, 16, (uint64_t *)d_sz, (uint64_t *)d_fo, d.stream()),
+          "lsm_sst_layout");
+    const size_t bound = nf * (lsm_filter_block_size(m) + 40 + 15) + 16 * fsc[nlog] + 4 * total;
+    void *d_out = d.Dev(17, pad16(bound));
+    const size_t bws = lsm_build_sst_workspace_bytes(nf, maxr, m, (uint32_t)k);
+    void *d_bws = d.Dev(18, bws);
+    check(lsm_build_sst_views(d.ctx(), (const uint8_t *)d_keys, (const uint64_t *)d_koff,
+                              (const uint8_t *)d_wal, (const lsm_rec_desc *)d_desc, nullptr,
+                              (const uint32_t *)d_idx, (const uint64_t *)d_voff, (const uint64_t *)d_fs, nf,
+                              maxr, m, (uint32_t)k, (uint8_t *)d_out, (const uint64_t *)d_fo, nullptr, d_bws,
+                              bws, d.stream()),
+          "lsm_build_sst_views");
+    std::vector<uint64_t> sz(nf), fo(nf + 1);
+    d.D2H(sz.data(), d_sz, nf * 8);
+    d.D2H(fo.data(), d_fo, (nf + 1) * 8);
+    d.Sync();
+    for (uint32_t f = 0; f < nf; f++) {
+        out[log_of[f]].resize(sz[f]);
+        d.D2H(out[log_of[f]].data(), (uint8_t *)d_out + fo[f], sz[f]);
+    }
+    d.Sync();
+    return out;
+}
+
 }  // namespace sstable
 }  // namespace golsm

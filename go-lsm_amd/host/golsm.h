@@ -88,7 +88,7 @@ class Device {
     void Sync();
 
   private:
-    static constexpr int kSlots = 12;
+    static constexpr int kSlots = 20;
     lsm_ctx *ctx_ = nullptr;
     void *stream_ = nullptr;
     void *dev_[kSlots] = {};
@@ -267,6 +267,19 @@ std::vector<Bytes> BuildImagesAt(const std::vector<kv::KeyValuePair> &sorted,
 // contract; container/heap's own order is unspecified).  The
 // tables are returned as decoded from their built images, level set.
 std::vector<SSTable> CompactAndMergeKVs(const std::vector<kv::KeyValuePair> &kvs, int level);
+// What Manager.CreateNewSSTable (sstable/manager.go:74-95) does for each
+// IMemTable -- BuildSSTableFromIMemTable (builder.go:22-31) over
+// IMemTable.RangeScan, then SSTable.EncodeTo -- for every memtable at once,
+// from the memtables' own WAL bytes instead of a walk of the skiplist:
+// lsm_wal_replay -> lsm_memtable_order -> lsm_gather_kvs_dev -> lsm_sst_layout
+// -> lsm_build_sst_views.  images[w] is log w's level-0 .sst image, empty when
+// its memtable delivers no pair or its replay failed ((*status)[w], the
+// lsm_status wal.Recover's error maps to).  scan: LSM_MEMTABLE_ALL (every
+// node, tombstones included) or LSM_MEMTABLE_RANGESCAN (RangeScan as written:
+// delivery stops at the first inner tombstone).
+std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int scan,
+                                         std::vector<int32_t> *status = nullptr,
+                                         uint64_t m = bloom::kDefaultM, uint64_t k = bloom::kDefaultK);
 
 }  // namespace sstable
 }  // namespace golsm

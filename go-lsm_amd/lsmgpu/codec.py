@@ -1148,3 +1148,117 @@ def build_sst_views_into(ctx: Context, batch: RecordBatch, sb: "SstBuild", d_byt
         _ptr(val_desc), _ptr(idx), _ptr(batch.voff), _ptr(sb.d_file_start), nf, sb.max_recs, sb.m,
         sb.k, _ptr(sb.out), _ptr(sb.d_file_off), _ptr(sb.footer), _ptr(sb.workspace),
         sb.workspace.numel(), _stream_handle(stream)), "lsm_build_sst_views")
+
+
+# ---- memtable flush (lsm_memtable_order) ---------------------------------------
+
+MEMTABLE_ALL, MEMTABLE_RANGESCAN = 0, 1  # enum lsm_memtable_scan
+MEMTABLE_TILE = 1024                     # LSM_MEMTABLE_TILE
+MEMTABLE_OVERFLOW = 1 << 63              # LSM_MEMTABLE_OVERFLOW, in counts[2]
+
+
+def memtable_order_workspace(ctx: Context, nlog: int, nslot: int, max_log_records: int) -> torch.Tensor:
+    n = int(ctx.lib.lsm_memtable_order_workspace_bytes(nlog, nslot, max_log_records))
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=ctx.torch_device)
+
+
+class MemtableOrder:
+    """lsm_memtable_order's buffers: idx[file_start[w]:file_start[w + 1]] = the
+    slots of log w's memtable nodes in key order.  file_start (nlog + 1) and
+    the three counts share one device tensor, so one copy reads both back."""
+
+    def __init__(self, ctx: Context, nlog: int, nslot: int, max_log_records: int):
+        dev = ctx.torch_device
+        self.nlog, self.nslot, self.max_log_records = nlog, nslot, max_log_records
+        self.idx = torch.empty(max(nslot, 1), dtype=torch.int32, device=dev)
+        self.fsc = torch.zeros(nlog + 1 + 3, dtype=torch.int64, device=dev)
+        self.file_start, self.counts = self.fsc[:nlog + 1], self.fsc[nlog + 1:]
+        self.workspace = memtable_order_workspace(ctx, nlog, nslot, max_log_records)
+
+    def result(self):
+        """(per-log slot arrays, counts {pairs, non-empty logs, most pairs in a
+        log}, overflow) on the host (reads back)."""
+        h = self.fsc.cpu().numpy().view(np.uint64)
+        fs, c = h[:self.nlog + 1].astype(np.int64), h[self.nlog + 1:]
+        idx = self.idx[:int(c[0])].cpu().numpy().view(np.uint32)
+        per_log = [idx[fs[w]:fs[w + 1]].copy() for w in range(self.nlog)]
+        over = bool(int(c[2]) & MEMTABLE_OVERFLOW)
+        return per_log, [int(c[0]), int(c[1]), int(c[2]) & (MEMTABLE_OVERFLOW - 1)], over
+
+
+def memtable_order_into(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, wal_off: torch.Tensor,
+                        scan: int, mo: MemtableOrder, stream=None) -> None:
+    """lsm_memtable_order over a WAL replay's outputs r (either placement)."""
+    _lib.check(ctx.lib.lsm_memtable_order(
+        ctx.handle, _ptr(d_wal), _ptr(r.desc), _ptr(r.rec_base), _ptr(wal_off), _ptr(r.nrec),
+        _ptr(r.status), mo.nlog, mo.nslot, mo.max_log_records, scan, _ptr(mo.idx),
+        _ptr(mo.file_start), _ptr(mo.counts), _ptr(mo.workspace), mo.workspace.numel(),
+        _stream_handle(stream)), "lsm_memtable_order")
+
+
+def memtable_order(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, wal_off: torch.Tensor,
+                   max_log_records: int, scan: int = MEMTABLE_ALL, stream=None) -> MemtableOrder:
+    """The memtables of the replayed logs: each log's last record per key, in
+    key order (MEMTABLE_ALL), or IMemTable.RangeScan's exact delivery
+    (MEMTABLE_RANGESCAN).  max_log_records: lsm_max_records(KV, max_wal_len)."""
+    mo = MemtableOrder(ctx, int(wal_off.numel()), int(r.desc.shape[0]), int(max_log_records))
+    if mo.nlog:
+        memtable_order_into(ctx, d_wal, r, wal_off, scan, mo, stream=stream)
+    return mo
+
+
+@dataclass
+class MemtableFlush:
+    """memtable_flush's result: image f is out[file_off[f]:file_off[f] +
+    file_len[f]] and holds the memtable of log `log[f]`; status[w] is log w's
+    replay status (a failed log has no image)."""
+    out: torch.Tensor
+    file_off: np.ndarray
+    file_len: np.ndarray
+    log: np.ndarray
+    status: np.ndarray
+    overflow: bool
+    order: MemtableOrder
+    replay: DecodeResult
+
+
+def memtable_flush(ctx: Context, d_wal: torch.Tensor, wal_off: torch.Tensor, wal_len: torch.Tensor,
+                   scan: int, m: int = DEFAULT_BLOOM_M, k: int = DEFAULT_BLOOM_K,
+                   max_len: Optional[int] = None, stream=None) -> MemtableFlush:
+    """CreateNewSSTable's image (sstable/manager.go:74-95) for every log at
+    once: lsm_wal_replay -> lsm_memtable_order -> lsm_gather_kvs_dev (keys) ->
+    lsm_sst_layout -> lsm_build_sst_views, the values read in place from the
+    WAL bytes.  One level-0 image per non-empty memtable; one read-back (the
+    order's file starts and counts) between the order and the build."""
+    dev = ctx.torch_device
+    nlog = int(wal_off.numel())
+    if max_len is None:
+        max_len = int(wal_len.max().item()) if nlog else 0
+    r = wal_replay(ctx, d_wal, wal_off, wal_len, max_len=max_len, stream=stream)
+    mo = memtable_order(ctx, d_wal, r, wal_off, int(ctx.lib.lsm_max_records(GRAMMAR_KV, max_len)),
+                        scan, stream=stream)
+    nbytes = int(d_wal.numel())
+    empty = np.zeros(0, np.uint64)
+    if nlog == 0:
+        return MemtableFlush(torch.zeros(pad16(0), dtype=torch.uint8, device=dev), empty, empty,
+                             np.zeros(0, np.int64), np.zeros(0, np.int32), False, mo, r)
+    batch = gather_kvs(ctx, d_wal, r.desc, None, mo.idx, min(mo.nslot, nbytes // 8), nbytes, None,
+                       stream=stream, d_nout=mo.counts[:1])
+    if stream is not None:
+        stream.synchronize()
+    h = mo.fsc.cpu().numpy().view(np.uint64)  # the one read-back
+    fs, c = h[:nlog + 1], h[nlog + 1:]
+    status = r.status[:nlog].cpu().numpy().copy()
+    logs = np.nonzero(np.diff(fs.astype(np.int64)) > 0)[0]
+    nfile, total = len(logs), int(c[0])
+    over = bool(int(c[2]) & MEMTABLE_OVERFLOW)
+    if nfile == 0:  # an empty memtable has no image (Go would reach EncodeTo with a nil Header)
+        return MemtableFlush(torch.zeros(pad16(0), dtype=torch.uint8, device=dev), empty, empty, logs,
+                             status, over, mo, r)
+    # the file list without the empty memtables: their starts repeat the next one's
+    d_fs = _dev_i64(np.concatenate([fs[logs], [np.uint64(total)]]).astype(np.uint64), dev)
+    batch.n = total
+    sb = prepare_sst_device(ctx, batch, d_fs, nfile, int(c[2]) & (MEMTABLE_OVERFLOW - 1),
+                            val_bytes=nbytes, m=m, k=k, stream=stream)
+    build_sst_views_into(ctx, batch, sb, d_wal, r.desc, None, mo.idx, stream=stream)
+    return MemtableFlush(sb.out, sb.file_off, sb.file_size, logs, status, over, mo, r)

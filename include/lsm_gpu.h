@@ -52,7 +52,8 @@ extern "C" {
  * lsm_build_flags.
  * Added within v7 (backward compatible, the version stays 7; a binding finds
  * them by symbol lookup): lsm_search and lsm_search_workspace_bytes
- * (Manager.Search over a whole tree in one call). */
+ * (Manager.Search over a whole tree in one call); lsm_memtable_order and
+ * lsm_memtable_order_workspace_bytes (a memtable's contents from its WAL). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -252,6 +253,60 @@ size_t lsm_wal_replay_workspace_bytes(uint32_t nwal, uint32_t max_wal_len);
 int lsm_wal_replay(lsm_ctx *ctx, const uint8_t *d_wal, const uint64_t *d_wal_off,
                    const uint32_t *d_wal_len, uint32_t nwal, uint32_t max_wal_len,
                    const lsm_decode_out *out, void *d_workspace, size_t ws_bytes, void *stream);
+
+/* ---- memtable flush (added within ABI 7) ----------------------------------- */
+
+/* The contents of nlog memtables from their WALs, in one asynchronous call:
+ * what IMemTable.RangeScan (memtable/imemtable.go:46-53) hands to
+ * BuildSSTableFromIMemTable (sstable/builder.go:22-31) on every eviction
+ * (sstable/manager.go:74-95) and on recovery (memtable/manager.go:140-180).
+ * A memtable is a skiplist in which a later Add of a key replaces the earlier
+ * pair (skiplist/skiplist.go:83-118), and MemTable.Insert appends to the WAL
+ * before AddPair (memtable.go:68-78), so its nodes are exactly the last
+ * record of each key of its log, in key order.
+ *
+ * Input: lsm_wal_replay's outputs as they are (KV descriptors d_desc into
+ * d_bytes, d_nrec, d_status) in either placement -- d_rec_base (nlog + 1
+ * entries), or NULL for offset addressing, base(w) = d_log_off[w] / 8.  nslot
+ * is the number of entries of d_desc (< 2^32 - 1); max_log_records bounds
+ * every d_nrec[w] (lsm_max_records(LSM_GRAMMAR_KV, max_wal_len); < 2^31) and,
+ * with nlog (<= 65535) and nslot, sizes every launch and the workspace.
+ *
+ * Per log w with d_status[w] == 0: its records sorted by key in Go string
+ * order (bytewise, unsigned, a proper prefix first; any key length), of equal
+ * keys the one at the greatest input position kept.  A log with a non-zero
+ * status contributes nothing (wal.Recover returned an error, memtable.go:
+ * 133-139; the caller has the status).  Logs never interact.  The kept
+ * records' slots (indices into d_desc) go to d_idx[d_file_start[w] ..
+ * d_file_start[w + 1]), dense across logs; d_idx holds as many entries as the
+ * logs have records (nslot always suffices).
+ *   LSM_MEMTABLE_ALL: every node, tombstones (kv.DeletedValue, kv.go:29-31:
+ *     a value of exactly those 13 bytes) included -- the memtable's whole
+ *     contents, and the mode to use.
+ *   LSM_MEMTABLE_RANGESCAN: RangeScan as written, `for SeekToFirst(); Valid();
+ *     Next()` (skiplist/iterator.go:27-33, 68-70): the tombstones at the front
+ *     are skipped and delivery STOPS before the first tombstone after that,
+ *     so the pairs behind it never reach the SSTable.  The reference's exact
+ *     output, as LSM_TIE_GOHEAP is for the merge; not the recommended mode.
+ * d_counts (device, 3 entries) = {pairs delivered, logs with at least one
+ * pair, the most pairs in one log} -- what the build's launch needs.  A log
+ * with d_nrec[w] > max_log_records (or whose records pass nslot) is not
+ * indexed: it gets no pairs and bit 63 of d_counts[2] is set.
+ * nlog == 0 returns 0 with nothing written.  No host synchronisation, no
+ * read-back and no device allocation: the call can be captured in a graph.
+ * Workspace: lsm_memtable_order_workspace_bytes (40 bytes per slot). */
+enum lsm_memtable_scan {
+    LSM_MEMTABLE_ALL = 0,       /* every node of the skiplist, tombstones included            */
+    LSM_MEMTABLE_RANGESCAN = 1, /* IMemTable.RangeScan as written (imemtable.go:46-53), exact */
+};
+#define LSM_MEMTABLE_TILE 1024 /* records sorted in LDS by one workgroup */
+#define LSM_MEMTABLE_OVERFLOW (1ull << 63) /* in d_counts[2] */
+size_t lsm_memtable_order_workspace_bytes(uint32_t nlog, uint64_t nslot, uint32_t max_log_records);
+int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                       const uint64_t *d_rec_base, const uint64_t *d_log_off, const uint32_t *d_nrec,
+                       const int32_t *d_status, uint32_t nlog, uint64_t nslot,
+                       uint32_t max_log_records, int scan, uint32_t *d_idx, uint64_t *d_file_start,
+                       uint64_t *d_counts, void *d_ws, size_t ws_bytes, void *stream);
 
 /* ---- whole .sst files ------------------------------------------------------ */
 
