@@ -3550,11 +3550,35 @@ struct SrShape {
     uint32_t start[kSrLevels + 1];
 };
 
-__global__ __launch_bounds__(256) void search_kernel(GetArgs a, const McFile *files, SrShape S,
-                                                     int32_t *level_out, int32_t *table_out) {
+// lsm_db_get's instantiation (DB): database.Get's second half.  A key the
+// memtables answered (db.mem_result, lsm_memtable_search's) does none of the
+// search -- no hash, no filter test, no Seek -- and keeps the value view the
+// memtable search wrote; the others run Search as below and db.src says where
+// Get's value lies.  lsm_search's kernel (search_body<false>) compiles none of
+// this and takes the arguments it always took.
+struct SrDb {
+    const int32_t *mem_result;
+    int32_t *src;
+    int mode;
+};
+
+template <bool DB>
+__device__ __forceinline__ void search_body(const GetArgs &a, const McFile *files, const SrShape &S,
+                                            int32_t *level_out, int32_t *table_out, const SrDb &db) {
     const uint32_t n0 = S.start[1];
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.nkeys;
          i += (uint64_t)gridDim.x * 256) {
+        if constexpr (DB) {
+            // database.go:29: `if value != nil` -- EXACT sends a tombstone's nil on to the tables
+            const int32_t m = db.mem_result[i];
+            if (m == LSM_MEM_VALUE || (m == LSM_MEM_DELETED && db.mode == LSM_DBGET_TOMBSTONE_HIDES)) {
+                a.result[i] = LSM_GET_ABSENT;
+                table_out[i] = -1;
+                level_out[i] = -1;
+                db.src[i] = LSM_SRC_MEMTABLE;
+                continue;
+            }
+        }
         const uint64_t k0 = a.koff[i], kl = a.koff[i + 1] - k0;
         const uint8_t *kp = a.keys + k0;
         uint32_t kw[4];
@@ -3608,7 +3632,19 @@ __global__ __launch_bounds__(256) void search_kernel(GetArgs a, const McFile *fi
         a.value[i] = v;
         table_out[i] = tab;
         level_out[i] = lev;
+        if constexpr (DB) db.src[i] = res == LSM_GET_ABSENT ? LSM_SRC_NONE : LSM_SRC_SSTABLE;
     }
+}
+
+// lsm_search's kernel: its arguments are what they were before lsm_db_get
+__global__ __launch_bounds__(256) void search_kernel(GetArgs a, const McFile *files, SrShape S,
+                                                     int32_t *level_out, int32_t *table_out) {
+    search_body<false>(a, files, S, level_out, table_out, SrDb{});
+}
+
+__global__ __launch_bounds__(256) void db_search_kernel(GetArgs a, const McFile *files, SrShape S,
+                                                        int32_t *level_out, int32_t *table_out, SrDb db) {
+    search_body<true>(a, files, S, level_out, table_out, db);
 }
 
 template <int G>
@@ -4435,6 +4471,58 @@ extern "C" int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_inde
     const uint64_t g = (nkeys + 255) / 256;
     const dim3 grid(g < kSrMaxGrid ? (uint32_t)g : kSrMaxGrid);
     hipLaunchKernelGGL(search_kernel, grid, dim3(256), 0, s, a, files, S, d_level, d_table);
+    LSM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" size_t lsm_db_get_workspace_bytes(const uint32_t *level_start, uint64_t nkeys) {
+    return lsm_search_workspace_bytes(level_start, nkeys);
+}
+
+extern "C" int lsm_db_get(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                          const uint32_t *d_idx, const uint64_t *d_file_start, uint32_t nlog,
+                          const void *d_mem_index, size_t mem_index_bytes, const uint8_t *d_img,
+                          const void *d_index, const uint32_t *level_start, const uint64_t *d_file_off,
+                          const uint64_t *d_file_len, const lsm_sst_meta *d_meta, const uint64_t *d_rec_base,
+                          const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value, const void *d_tree,
+                          uint32_t tree_nidx, size_t tree_bytes, const uint8_t *d_keys,
+                          const uint64_t *d_koff, uint64_t nkeys, int mode, int32_t *d_mem_result,
+                          int32_t *d_log, uint32_t *d_slot, int32_t *d_level, int32_t *d_table,
+                          int32_t *d_result, lsm_rec_desc *d_value, int32_t *d_src, void *d_workspace,
+                          size_t ws_bytes, void *stream) {
+    if (!ctx || (mode != LSM_DBGET_EXACT && mode != LSM_DBGET_TOMBSTONE_HIDES)) return LSM_EINVAL;
+    if (nkeys == 0) return 0;
+    SrShape S{};
+    if (!level_start || !search_shape(level_start, S)) return LSM_EINVAL;
+    if (!d_keys || !d_koff || !d_level || !d_table || !d_result || !d_value || !d_src) return LSM_EINVAL;
+    const uint32_t nfile = S.start[kSrLevels];
+    // an empty tree needs none of the tree's buffers: every level of S is empty
+    // and the kernel reads no table
+    GetArgs a{};
+    if (nfile) {
+        if (!d_img || !d_index || !d_file_off || !d_file_len || !d_meta || !d_idx_desc || !d_idx_value ||
+            !d_workspace)
+            return LSM_EINVAL;
+        if (ws_bytes < kSrWsBytes) return LSM_ESPACE;
+        a = get_args(d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc, d_idx_value);
+        const int rc = get_tree_args(a, nfile, d_tree, tree_nidx, tree_bytes);
+        if (rc) return rc;
+    }
+    a.keys = d_keys;
+    a.koff = d_koff;
+    a.nkeys = nkeys;
+    a.result = d_result;
+    a.value = d_value;
+    // every check of both halves is made before the first launch
+    const int rc = lsm_memtable_search(ctx, d_bytes, d_desc, d_idx, d_file_start, nlog, d_mem_index,
+                                       mem_index_bytes, d_keys, d_koff, nkeys, d_mem_result, d_log, d_slot,
+                                       d_value, stream);
+    if (rc) return rc;
+    const uint64_t g = (nkeys + 255) / 256;
+    const dim3 grid(g < kSrMaxGrid ? (uint32_t)g : kSrMaxGrid);
+    hipLaunchKernelGGL(db_search_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a,
+                       static_cast<const McFile *>(d_index), S, d_level, d_table,
+                       SrDb{d_mem_result, d_src, mode});
     LSM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -106,15 +106,16 @@ __device__ __forceinline__ bool item_less(const Logs &L, Key16 ka, uint32_t a, K
 }
 
 // kv.DeletedValue (kv/kv.go:29-31), 13 bytes; IsDeleted compares the whole value.
-__device__ bool is_tombstone(const Logs &L, uint32_t slot) {
-    const lsm_rec_desc d = L.desc[slot];
+__device__ bool is_tombstone_rec(const uint8_t *bytes, const lsm_rec_desc d) {
     if (d.val_len != 13) return false;
     const uint8_t t[13] = {0xEF, 0xBD, 0x9E, 'D', 'E', 'L', 'E', 'T', 'E', 'D', 0xEF, 0xBD, 0x9E};
-    const uint8_t *v = L.bytes + d.rec_off + 8 + d.key_len;
+    const uint8_t *v = bytes + d.rec_off + 8 + d.key_len;
     bool eq = true;
     for (int i = 0; i < 13; i++) eq &= v[i] == t[i];
     return eq;
 }
+
+__device__ bool is_tombstone(const Logs &L, uint32_t slot) { return is_tombstone_rec(L.bytes, L.desc[slot]); }
 
 // ---- tile sort: one workgroup per tile of one log --------------------------
 
@@ -393,6 +394,133 @@ __global__ __launch_bounds__(kThreads) void mt_emit(Logs L, const uint32_t *pos,
     idx[file_start[w] + (r - l)] = pos[base + i];
 }
 
+// ---- search: memtable.Manager.Search over the ordered memtables -------------
+//
+// SkipList.Search (skiplist.go:60-79) finds the node with exactly the key;
+// Manager.Search (memtable/manager.go:61-74) asks Mem, then IMems newest
+// first, and the first table that holds the key ends the search, tombstone or
+// not.  A memtable here is its log's slice of d_idx (lsm_memtable_order,
+// LSM_MEMTABLE_ALL): the nodes in key order, so the skiplist's walk is a
+// bisection (its steps are not observable).  One thread per key runs the
+// whole of Manager.Search, log nlog - 1 down to 0.  Keys are unique within a
+// log, so a three-way compare ends the bisection on the first equal node.
+// Without the index a step is three dependent loads (d_idx -> d_desc -> key
+// bytes); the index holds each node's Key16 in d_idx order, one 16-byte
+// gather per step, the node itself only on a 16-byte tie.
+constexpr uint32_t kMsMaxGrid = 2048;  // workgroups: 2,048 resident threads on each of 256 CUs
+constexpr size_t kMsHeader = 256;      // the index's header: {nodes indexed}, padded to 256 bytes
+
+struct MsArgs {
+    const uint8_t *bytes;
+    const lsm_rec_desc *desc;
+    const uint32_t *idx;
+    const uint64_t *file_start;
+    uint32_t nlog;
+    const uint64_t *index_hdr;  // or NULL: no index
+    const Key16 *index;
+    uint64_t index_cap;  // nodes the index buffer has room for
+    const uint8_t *keys;
+    const uint64_t *koff;
+    uint64_t nkeys;
+    int32_t *mem_result, *log;
+    uint32_t *slot;
+    lsm_rec_desc *value;
+};
+
+// Keys (pa, la) and (pb, lb) whose first 16 bytes are equal: key_cmp_tail
+// with either key anywhere (a node against a probe key).
+__device__ int key_cmp_tail_at(const uint8_t *pa, uint32_t la, const uint8_t *pb, uint32_t lb) {
+    const uint32_t lm = la < lb ? la : lb;
+    for (uint32_t j = 16; j < lm; j += 8) {
+        const uint64_t x = key_word(pa, lm, j), y = key_word(pb, lm, j);
+        if (x != y) return x < y ? -1 : 1;
+    }
+    return la == lb ? 0 : (la < lb ? -1 : 1);
+}
+
+__global__ __launch_bounds__(kThreads) void mt_search(MsArgs a) {
+    // the nodes the index vouches for: those its build wrote, within the buffer
+    uint64_t nindexed = 0;
+    if (a.index_hdr) {
+        nindexed = a.index_hdr[0];
+        nindexed = nindexed < a.index_cap ? nindexed : a.index_cap;
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < a.nkeys;
+         i += (uint64_t)gridDim.x * kThreads) {
+        const uint64_t k0 = a.koff[i], kl64 = a.koff[i + 1] - k0;
+        int32_t res = LSM_MEM_MISS, lg = -1;
+        uint32_t sl = kPad;
+        lsm_rec_desc v{0, 0, 0};
+        // a node's key is at most kKeyCap bytes (kv.go:84): a longer probe equals none
+        if (kl64 <= kKeyCap) {
+            const uint32_t kl = (uint32_t)kl64;
+            const uint8_t *kp = a.keys + k0;
+            const Key16 pk{key_word(kp, kl, 0), key_word(kp, kl, 8)};
+            for (uint32_t w = a.nlog; w-- > 0 && res == LSM_MEM_MISS;) {
+                uint64_t lo = a.file_start[w], hi = a.file_start[w + 1];
+                const bool indexed = hi <= nindexed;
+                while (lo < hi) {
+                    const uint64_t mid = lo + (hi - lo) / 2;
+                    uint32_t s = kPad;
+                    lsm_rec_desc d{0, 0, 0};
+                    Key16 nk;
+                    if (indexed) {
+                        nk = a.index[mid];
+                    } else {
+                        s = a.idx[mid];
+                        d = a.desc[s];
+                        const uint8_t *np = a.bytes + d.rec_off + 4;
+                        nk = Key16{key_word(np, d.key_len, 0), key_word(np, d.key_len, 8)};
+                    }
+                    int c;
+                    if (nk.hi != pk.hi) c = nk.hi < pk.hi ? -1 : 1;
+                    else if (nk.lo != pk.lo) c = nk.lo < pk.lo ? -1 : 1;
+                    else {
+                        if (indexed) {
+                            s = a.idx[mid];
+                            d = a.desc[s];
+                        }
+                        c = key_cmp_tail_at(a.bytes + d.rec_off + 4, d.key_len, kp, kl);
+                    }
+                    if (c == 0) {  // (value, true), or (nil, true) for a tombstone: the search ends
+                        lg = (int32_t)w;
+                        sl = s;
+                        if (is_tombstone_rec(a.bytes, d)) {
+                            res = LSM_MEM_DELETED;
+                        } else {
+                            res = LSM_MEM_VALUE;
+                            v = lsm_rec_desc{d.rec_off + 4 + d.key_len, 0, d.val_len};
+                        }
+                        break;
+                    }
+                    if (c < 0) lo = mid + 1;
+                    else hi = mid;
+                }
+            }
+        }
+        a.mem_result[i] = res;
+        a.log[i] = lg;
+        a.slot[i] = sl;
+        a.value[i] = v;
+    }
+}
+
+// index[p] = the Key16 of node d_idx[p], p < d_file_start[nlog] (read here)
+// and < cap; the header records how many were written.
+__global__ __launch_bounds__(kThreads) void mt_index_build(const uint8_t *bytes, const lsm_rec_desc *desc,
+                                                          const uint32_t *idx, const uint64_t *file_start,
+                                                          uint32_t nlog, uint64_t cap, uint64_t *hdr,
+                                                          Key16 *index) {
+    uint64_t n = file_start[nlog];
+    n = n < cap ? n : cap;
+    if (blockIdx.x == 0 && threadIdx.x == 0) hdr[0] = n;
+    for (uint64_t p = (uint64_t)blockIdx.x * kThreads + threadIdx.x; p < n; p += (uint64_t)gridDim.x * kThreads) {
+        const lsm_rec_desc d = desc[idx[p]];
+        const uint8_t *key = bytes + d.rec_off + 4;
+        index[p] = Key16{key_word(key, d.key_len, 0), key_word(key, d.key_len, 8)};
+    }
+}
+
 struct Ws {
     Key16 *key[2];
     uint32_t *pos[2];
@@ -477,6 +605,65 @@ extern "C" int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const ls
     if (nblk)
         hipLaunchKernelGGL(mt_emit, dim3(nblk, nlog), dim3(kThreads), 0, s, L, ws.pos[cur], flag, ws.lead,
                            ws.cut, d_file_start, d_idx);
+    LSM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" size_t lsm_memtable_search_index_bytes(uint64_t nnode_max) {
+    return nnode_max ? kMsHeader + sizeof(Key16) * (size_t)nnode_max : 0;
+}
+
+extern "C" int lsm_memtable_search_index_build(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                                               const uint32_t *d_idx, const uint64_t *d_file_start,
+                                               uint32_t nlog, uint64_t nnode_max, void *d_index,
+                                               size_t index_bytes, void *stream) {
+    if (!ctx) return LSM_EINVAL;
+    if (nlog == 0 || nnode_max == 0) return 0;
+    if (nlog > 65535 || nnode_max >= 0xFFFFFFFFull || !d_bytes || !d_desc || !d_idx || !d_file_start)
+        return LSM_EINVAL;
+    if (!d_index || index_bytes < lsm_memtable_search_index_bytes(nnode_max)) return LSM_ESPACE;
+    uint8_t *p = static_cast<uint8_t *>(d_index);
+    const uint64_t g = (nnode_max + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(mt_index_build, dim3(g < kMsMaxGrid ? (uint32_t)g : kMsMaxGrid), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), d_bytes, d_desc, d_idx, d_file_start, nlog, nnode_max,
+                       reinterpret_cast<uint64_t *>(p), reinterpret_cast<Key16 *>(p + kMsHeader));
+    LSM_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int lsm_memtable_search(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                                   const uint32_t *d_idx, const uint64_t *d_file_start, uint32_t nlog,
+                                   const void *d_index, size_t index_bytes, const uint8_t *d_keys,
+                                   const uint64_t *d_koff, uint64_t nkeys, int32_t *d_mem_result,
+                                   int32_t *d_log, uint32_t *d_slot, lsm_rec_desc *d_value, void *stream) {
+    if (!ctx) return LSM_EINVAL;
+    if (nkeys == 0) return 0;
+    if (nlog > 65535 || !d_keys || !d_koff || !d_mem_result || !d_log || !d_slot || !d_value)
+        return LSM_EINVAL;
+    if (nlog && (!d_bytes || !d_desc || !d_idx || !d_file_start)) return LSM_EINVAL;
+    if (d_index && index_bytes < lsm_memtable_search_index_bytes(1)) return LSM_ESPACE;
+    MsArgs a{};
+    a.bytes = d_bytes;
+    a.desc = d_desc;
+    a.idx = d_idx;
+    a.file_start = d_file_start;
+    a.nlog = nlog;
+    if (d_index && nlog) {
+        const uint8_t *p = static_cast<const uint8_t *>(d_index);
+        a.index_hdr = reinterpret_cast<const uint64_t *>(p);
+        a.index = reinterpret_cast<const Key16 *>(p + kMsHeader);
+        a.index_cap = (index_bytes - kMsHeader) / sizeof(Key16);
+    }
+    a.keys = d_keys;
+    a.koff = d_koff;
+    a.nkeys = nkeys;
+    a.mem_result = d_mem_result;
+    a.log = d_log;
+    a.slot = d_slot;
+    a.value = d_value;
+    const uint64_t g = (nkeys + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(mt_search, dim3(g < kMsMaxGrid ? (uint32_t)g : kMsMaxGrid), dim3(kThreads), 0,
+                       static_cast<hipStream_t>(stream), a);
     LSM_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -940,13 +940,20 @@ std::vector<SSTable> CompactAndMergeKVs(const std::vector<kv::KeyValuePair> &kvs
     return results;
 }
 
-std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int scan,
-                                         std::vector<int32_t> *status, uint64_t m, uint64_t k) {
-    const size_t nlog = wals.size();
-    std::vector<Bytes> out(nlog);
-    if (status) status->assign(nlog, 0);
-    if (nlog == 0) return out;  // nothing to flush: no device call
-    Device &d = Device::ThisThread();
+// wal.Recover of every log and the memtables' order on the device (slots 0-9):
+// lsm_wal_replay (offset-addressed: log w's records at slot off[w] / 8), then
+// lsm_memtable_order.  h = the logs as uploaded (pinned host copy).
+struct OrderedWALs {
+    size_t nlog, total;
+    uint64_t nslot;
+    uint8_t *h;
+    void *d_wal, *d_desc, *d_st, *d_idx;
+    uint64_t *d_fsc;  // file starts (nlog + 1), then the three counts
+};
+
+static OrderedWALs ReplayAndOrder(Device &d, const std::vector<Bytes> &wals, int scan) {
+    OrderedWALs r{};
+    const size_t nlog = r.nlog = wals.size();
     std::vector<uint64_t> off(nlog);
     std::vector<uint32_t> len(nlog);
     size_t total = 0, max_len = 0;
@@ -956,19 +963,19 @@ std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int sca
         max_len = std::max(max_len, wals[w].size());
         total += (wals[w].size() + 15) & ~(size_t)15;
     }
-    uint8_t *h = (uint8_t *)d.Host(0, pad16(total));
+    r.total = total;
+    uint8_t *h = r.h = (uint8_t *)d.Host(0, pad16(total));
     std::memset(h, 0, pad16(total));
     for (size_t w = 0; w < nlog; w++)
         if (!wals[w].empty()) std::memcpy(h + off[w], wals[w].data(), wals[w].size());
-    // wal.Recover of every log (offset-addressed: log w's records at slot off[w] / 8)
-    const uint64_t nslot = total / 8 + 1;
+    const uint64_t nslot = r.nslot = total / 8 + 1;
     const uint32_t maxrec = (uint32_t)lsm_max_records(LSM_GRAMMAR_KV, max_len);
-    void *d_wal = d.Dev(0, pad16(total));
+    void *d_wal = r.d_wal = d.Dev(0, pad16(total));
     void *d_off = d.Dev(1, nlog * 8);
     void *d_len = d.Dev(2, nlog * 4);
-    void *d_desc = d.Dev(3, nslot * sizeof(lsm_rec_desc));
+    void *d_desc = r.d_desc = d.Dev(3, nslot * sizeof(lsm_rec_desc));
     void *d_nrec = d.Dev(4, nlog * 4);
-    void *d_st = d.Dev(5, nlog * 4);
+    void *d_st = r.d_st = d.Dev(5, nlog * 4);
     const size_t wws = lsm_wal_replay_workspace_bytes((uint32_t)nlog, (uint32_t)max_len);
     void *d_wws = d.Dev(6, wws);
     d.H2D(d_wal, h, pad16(total));
@@ -982,8 +989,8 @@ std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int sca
                          (uint32_t)nlog, (uint32_t)max_len, &o, d_wws, wws, d.stream()),
           "lsm_wal_replay");
     // the memtables: each log's last record per key, in key order
-    void *d_idx = d.Dev(7, nslot * 4);
-    uint64_t *d_fsc = (uint64_t *)d.Dev(8, (nlog + 1 + 3) * 8);  // file starts, then the counts
+    void *d_idx = r.d_idx = d.Dev(7, nslot * 4);
+    uint64_t *d_fsc = r.d_fsc = (uint64_t *)d.Dev(8, (nlog + 1 + 3) * 8);
     const size_t ows = lsm_memtable_order_workspace_bytes((uint32_t)nlog, nslot, maxrec);
     void *d_ows = d.Dev(9, ows);
     check(lsm_memtable_order(d.ctx(), (const uint8_t *)d_wal, (const lsm_rec_desc *)d_desc, nullptr,
@@ -991,6 +998,21 @@ std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int sca
                              (uint32_t)nlog, nslot, maxrec, scan, (uint32_t *)d_idx, d_fsc,
                              d_fsc + nlog + 1, d_ows, ows, d.stream()),
           "lsm_memtable_order");
+    return r;
+}
+
+std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int scan,
+                                         std::vector<int32_t> *status, uint64_t m, uint64_t k) {
+    const size_t nlog = wals.size();
+    std::vector<Bytes> out(nlog);
+    if (status) status->assign(nlog, 0);
+    if (nlog == 0) return out;  // nothing to flush: no device call
+    Device &d = Device::ThisThread();
+    const OrderedWALs r = ReplayAndOrder(d, wals, scan);
+    const size_t total = r.total;
+    const uint64_t nslot = r.nslot;
+    void *d_wal = r.d_wal, *d_desc = r.d_desc, *d_st = r.d_st, *d_idx = r.d_idx;
+    uint64_t *d_fsc = r.d_fsc;
     // their keys packed; the values stay in the WAL bytes
     const uint64_t nout_max = std::min<uint64_t>(nslot, total / 8);
     void *d_keys = d.Dev(10, pad16(total));
@@ -1050,4 +1072,174 @@ std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int sca
 }
 
 }  // namespace sstable
+
+namespace memtables {
+
+std::vector<SearchResult> SearchWALs(const std::vector<Bytes> &wals, const std::vector<kv::Key> &keys) {
+    std::vector<SearchResult> out(keys.size());
+    if (wals.empty() || keys.empty()) return out;  // every key misses: no device call
+    Device &d = Device::ThisThread();
+    const sstable::OrderedWALs r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
+    const size_t nkeys = keys.size();
+    std::vector<uint64_t> koff(nkeys + 1, 0);
+    for (size_t i = 0; i < nkeys; i++) koff[i + 1] = koff[i] + keys[i].size();
+    const size_t kbytes = koff[nkeys];
+    uint8_t *hk = (uint8_t *)d.Host(1, pad16(kbytes));
+    std::memset(hk, 0, pad16(kbytes));
+    for (size_t i = 0; i < nkeys; i++) std::memcpy(hk + koff[i], keys[i].data(), keys[i].size());
+    void *d_keys = d.Dev(10, pad16(kbytes));
+    void *d_koff = d.Dev(11, (nkeys + 1) * 8);
+    void *d_res = d.Dev(12, nkeys * 4);
+    void *d_log = d.Dev(13, nkeys * 4);
+    void *d_slot = d.Dev(14, nkeys * 4);
+    void *d_val = d.Dev(15, nkeys * sizeof(lsm_rec_desc));
+    const size_t ib = lsm_memtable_search_index_bytes(r.nslot);
+    void *d_index = d.Dev(16, ib);
+    d.H2D(d_keys, hk, pad16(kbytes));
+    d.H2D(d_koff, koff.data(), (nkeys + 1) * 8);
+    check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
+                                          (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)r.nlog, r.nslot,
+                                          d_index, ib, d.stream()),
+          "lsm_memtable_search_index_build");
+    check(lsm_memtable_search(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
+                              (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)r.nlog, d_index, ib,
+                              (const uint8_t *)d_keys, (const uint64_t *)d_koff, nkeys, (int32_t *)d_res,
+                              (int32_t *)d_log, (uint32_t *)d_slot, (lsm_rec_desc *)d_val, d.stream()),
+          "lsm_memtable_search");
+    std::vector<int32_t> res(nkeys), log(nkeys);
+    std::vector<lsm_rec_desc> val(nkeys);
+    d.D2H(res.data(), d_res, nkeys * 4);
+    d.D2H(log.data(), d_log, nkeys * 4);
+    d.D2H(val.data(), d_val, nkeys * sizeof(lsm_rec_desc));
+    d.Sync();
+    for (size_t i = 0; i < nkeys; i++) {
+        out[i].result = res[i];
+        out[i].log = log[i];
+        if (res[i] == LSM_MEM_VALUE)  // the view is into the uploaded logs
+            out[i].value.assign(r.h + val[i].rec_off + 4, r.h + val[i].rec_off + 4 + val[i].val_len);
+    }
+    return out;
+}
+
+}  // namespace memtables
+
+namespace database {
+
+std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
+                                   const uint32_t *level_start, const std::vector<kv::Key> &keys,
+                                   int mode) {
+    if (mode != LSM_DBGET_EXACT && mode != LSM_DBGET_TOMBSTONE_HIDES)
+        throw std::invalid_argument("GetFromWALs: unknown mode");
+    if (!level_start || level_start[LSM_SEARCH_LEVELS] != images.size())
+        throw std::invalid_argument("GetFromWALs: level_start does not end at the number of images");
+    std::vector<GetResult> out(keys.size());
+    // no memtable and no table: every Get is (nil, nil); no device call
+    if (keys.empty() || (wals.empty() && images.empty())) return out;
+    Device &d = Device::ThisThread();
+    const size_t nkeys = keys.size(), nlog = wals.size(), nfile = images.size();
+    // the memtables (slots 0-9 and 16), when there are logs
+    sstable::OrderedWALs r{};
+    void *d_mem_index = nullptr;
+    size_t ib = 0;
+    if (nlog) {
+        r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
+        ib = lsm_memtable_search_index_bytes(r.nslot);
+        d_mem_index = d.Dev(16, ib);
+        check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
+                                              (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)nlog, r.nslot,
+                                              d_mem_index, ib, d.stream()),
+              "lsm_memtable_search_index_build");
+    }
+    // the tree (slots 20-28): the images in one buffer, decoded, and the sparse index over them
+    std::vector<uint64_t> off(nfile), len(nfile);
+    uint8_t *h_img = nullptr;
+    void *d_img = nullptr, *d_off = nullptr, *d_len = nullptr, *d_meta = nullptr, *d_idesc = nullptr,
+         *d_ival = nullptr, *d_index = nullptr;
+    if (nfile) {
+        size_t total = 0;
+        for (size_t f = 0; f < nfile; f++) {
+            off[f] = total;
+            len[f] = images[f].size();
+            total += (images[f].size() + 15) & ~(size_t)15;
+        }
+        h_img = (uint8_t *)d.Host(2, pad16(total));
+        std::memset(h_img, 0, pad16(total));
+        for (size_t f = 0; f < nfile; f++) std::memcpy(h_img + off[f], images[f].data(), images[f].size());
+        const size_t cap = total / 4 + 1;
+        d_img = d.Dev(20, pad16(total));
+        d_off = d.Dev(21, nfile * 8);
+        d_len = d.Dev(22, nfile * 8);
+        d_meta = d.Dev(23, nfile * sizeof(lsm_sst_meta));
+        d_idesc = d.Dev(24, cap * sizeof(lsm_rec_desc));
+        d_ival = d.Dev(25, cap * 8);
+        void *d_ddesc = d.Dev(26, cap * sizeof(lsm_rec_desc));
+        const size_t dws = lsm_decode_sst_workspace_bytes((uint32_t)nfile);
+        void *d_dws = d.Dev(27, dws);
+        d.H2D(d_img, h_img, pad16(total));
+        d.H2D(d_off, off.data(), nfile * 8);
+        d.H2D(d_len, len.data(), nfile * 8);
+        check(lsm_decode_sst(d.ctx(), (const uint8_t *)d_img, (const uint64_t *)d_off, (const uint64_t *)d_len,
+                             (uint32_t)nfile, nullptr, (lsm_sst_meta *)d_meta, (lsm_rec_desc *)d_idesc,
+                             (int64_t *)d_ival, (lsm_rec_desc *)d_ddesc, d_dws, dws, d.stream()),
+              "lsm_decode_sst");
+        d_index = d.Dev(28, lsm_level_index_bytes((uint32_t)nfile));
+        check(lsm_level_index_build(d.ctx(), (const uint8_t *)d_img, (const uint64_t *)d_off,
+                                    (const lsm_sst_meta *)d_meta, (uint32_t)nfile, d_index, d.stream()),
+              "lsm_level_index_build");
+    }
+    // the keys (slots 10-11) and the outputs (12-15, 30-33)
+    std::vector<uint64_t> koff(nkeys + 1, 0);
+    for (size_t i = 0; i < nkeys; i++) koff[i + 1] = koff[i] + keys[i].size();
+    const size_t kbytes = koff[nkeys];
+    uint8_t *hk = (uint8_t *)d.Host(1, pad16(kbytes));
+    std::memset(hk, 0, pad16(kbytes));
+    for (size_t i = 0; i < nkeys; i++) std::memcpy(hk + koff[i], keys[i].data(), keys[i].size());
+    void *d_keys = d.Dev(10, pad16(kbytes));
+    void *d_koff = d.Dev(11, (nkeys + 1) * 8);
+    void *d_res = d.Dev(12, nkeys * 4), *d_log = d.Dev(13, nkeys * 4), *d_slot = d.Dev(14, nkeys * 4);
+    void *d_val = d.Dev(15, nkeys * sizeof(lsm_rec_desc));
+    void *d_level = d.Dev(30, nkeys * 4), *d_table = d.Dev(31, nkeys * 4), *d_tres = d.Dev(32, nkeys * 4);
+    void *d_src = d.Dev(33, nkeys * 4);
+    const size_t ws = lsm_db_get_workspace_bytes(level_start, nkeys);
+    void *d_ws = d.Dev(34, ws ? ws : 16);
+    d.H2D(d_keys, hk, pad16(kbytes));
+    d.H2D(d_koff, koff.data(), (nkeys + 1) * 8);
+    // no Seek tree: the Seek walks each table's decoded index (the same answers)
+    check(lsm_db_get(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
+                     (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)nlog, d_mem_index, ib,
+                     (const uint8_t *)d_img, d_index, level_start, (const uint64_t *)d_off,
+                     (const uint64_t *)d_len, (const lsm_sst_meta *)d_meta, nullptr,
+                     (const lsm_rec_desc *)d_idesc, (const int64_t *)d_ival, nullptr, 0, 0,
+                     (const uint8_t *)d_keys, (const uint64_t *)d_koff, nkeys, mode, (int32_t *)d_res,
+                     (int32_t *)d_log, (uint32_t *)d_slot, (int32_t *)d_level, (int32_t *)d_table,
+                     (int32_t *)d_tres, (lsm_rec_desc *)d_val, (int32_t *)d_src, d_ws, ws, d.stream()),
+          "lsm_db_get");
+    std::vector<int32_t> res(nkeys), log(nkeys), level(nkeys), table(nkeys), tres(nkeys), src(nkeys);
+    std::vector<lsm_rec_desc> val(nkeys);
+    d.D2H(res.data(), d_res, nkeys * 4);
+    d.D2H(log.data(), d_log, nkeys * 4);
+    d.D2H(level.data(), d_level, nkeys * 4);
+    d.D2H(table.data(), d_table, nkeys * 4);
+    d.D2H(tres.data(), d_tres, nkeys * 4);
+    d.D2H(src.data(), d_src, nkeys * 4);
+    d.D2H(val.data(), d_val, nkeys * sizeof(lsm_rec_desc));
+    d.Sync();
+    for (size_t i = 0; i < nkeys; i++) {
+        GetResult &g = out[i];
+        g.src = src[i];
+        g.mem_result = res[i];
+        g.log = log[i];
+        g.level = level[i];
+        g.table = table[i];
+        g.result = tres[i];
+        // d_src says which buffer the view is into: the logs or the images
+        const uint8_t *base = src[i] == LSM_SRC_MEMTABLE ? r.h : src[i] == LSM_SRC_SSTABLE ? h_img : nullptr;
+        const bool has = src[i] == LSM_SRC_MEMTABLE ? res[i] == LSM_MEM_VALUE
+                                                    : src[i] == LSM_SRC_SSTABLE && tres[i] == LSM_GET_FOUND;
+        if (base && has) g.value.assign(base + val[i].rec_off + 4, base + val[i].rec_off + 4 + val[i].val_len);
+    }
+    return out;
+}
+
+}  // namespace database
 }  // namespace golsm

@@ -88,7 +88,7 @@ class Device {
     void Sync();
 
   private:
-    static constexpr int kSlots = 20;
+    static constexpr int kSlots = 40;
     lsm_ctx *ctx_ = nullptr;
     void *stream_ = nullptr;
     void *dev_[kSlots] = {};
@@ -282,4 +282,50 @@ std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int sca
                                          uint64_t m = bloom::kDefaultM, uint64_t k = bloom::kDefaultK);
 
 }  // namespace sstable
+
+// Go's package is `memtable`; the namespace is `memtables` because a mirror
+// test that does `using namespace golsm` has a function named `memtable`
+// (tests/cpp/memtable_mirror_test.cpp), which the package's name would hide.
+namespace memtables {
+// Manager.Search (memtable/manager.go:61-74) of every key over the memtables
+// recovered from `wals` (oldest first; the last is Mem, manager.go:140-180):
+// lsm_wal_replay -> lsm_memtable_order (LSM_MEMTABLE_ALL) ->
+// lsm_memtable_search_index_build -> lsm_memtable_search.  The newest log
+// holding the key answers: result is a lsm_mem_result, log that log (-1 on a
+// miss), value the node's value for LSM_MEM_VALUE (empty for a tombstone: Go's
+// nil).  No logs or no keys: every key misses, no device call.
+struct SearchResult {
+    int32_t result = LSM_MEM_MISS;
+    int32_t log = -1;
+    kv::Value value;
+};
+std::vector<SearchResult> SearchWALs(const std::vector<Bytes> &wals, const std::vector<kv::Key> &keys);
+}  // namespace memtables
+
+namespace database {
+// database.Get (database/database.go:24-40) of every key over lsm_db_get: the
+// memtables recovered from `wals` (as memtables::SearchWALs), then
+// sstable.Manager.Search over `images` -- the tree's tables in lsm_search's
+// order (level 0 newest first, each deeper level by MinKey), level_start
+// (LSM_SEARCH_LEVELS + 1 entries) ending at images.size().  mode is a
+// lsm_db_get_mode.  src is a lsm_get_source and says where Get's value came
+// from: LSM_SRC_MEMTABLE (value copied from the logs), LSM_SRC_SSTABLE (from
+// the images; result > LSM_GET_FOUND is Search's error and value is empty),
+// LSM_SRC_NONE for (nil, nil).  mem_result / log as SearchWALs; level / table /
+// result as lsm_search for the keys that went on to the tables, -1 / -1 /
+// LSM_GET_ABSENT for the others.  No keys, or neither logs nor images: no
+// device call.  Throws std::invalid_argument for an unknown mode or a
+// level_start that does not end at images.size().
+struct GetResult {
+    int32_t src = LSM_SRC_NONE;
+    int32_t mem_result = LSM_MEM_MISS;
+    int32_t log = -1;
+    int32_t level = -1, table = -1;
+    int32_t result = LSM_GET_ABSENT;
+    kv::Value value;
+};
+std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
+                                   const uint32_t *level_start, const std::vector<kv::Key> &keys,
+                                   int mode = LSM_DBGET_TOMBSTONE_HIDES);
+}  // namespace database
 }  // namespace golsm

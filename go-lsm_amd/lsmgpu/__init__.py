@@ -20,5 +20,7 @@ from .codec import (  # noqa: F401
     TIE_INPUT, TIE_GOHEAP, goheap_pop_order,
     SstStream, prepare_sst_stream, build_sst_stream, build_sst_stream_into, segment_files_device,
     MEMTABLE_ALL, MEMTABLE_RANGESCAN, MEMTABLE_TILE, MEMTABLE_OVERFLOW, MemtableOrder, MemtableFlush,
-    memtable_order, memtable_order_into, memtable_order_workspace, memtable_flush)
+    memtable_order, memtable_order_into, memtable_order_workspace, memtable_flush,
+    MEM_MISS, MEM_VALUE, MEM_DELETED, DBGET_EXACT, DBGET_TOMBSTONE_HIDES, SRC_NONE, SRC_MEMTABLE,
+    SRC_SSTABLE, memtable_search_index, memtable_search, memtable_search_into, DbGet, alloc_db_get, db_get, db_get_into)
 from . import synth  # noqa: F401

@@ -100,6 +100,29 @@ SIGNATURES = {
                                           c_u32p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64,
                                           ctypes.c_uint32, ctypes.c_int, c_u32p, c_u64p, c_u64p,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "lsm_memtable_search_index_bytes": (ctypes.c_size_t, [ctypes.c_uint64]),
+    "lsm_memtable_search_index_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, ctypes.c_void_p, c_u32p,
+                                                       c_u64p, ctypes.c_uint32, ctypes.c_uint64,
+                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "lsm_memtable_search": (ctypes.c_int, [ctypes.c_void_p, c_u8p, ctypes.c_void_p, c_u32p, c_u64p,
+                                           ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, c_u8p,
+                                           c_u64p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
+                                           c_u32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "lsm_db_get_workspace_bytes": (ctypes.c_size_t, [c_u32p, ctypes.c_uint64]),
+    "lsm_db_get": (ctypes.c_int, [ctypes.c_void_p,
+                                  # the memtables
+                                  c_u8p, ctypes.c_void_p, c_u32p, c_u64p, ctypes.c_uint32,
+                                  ctypes.c_void_p, ctypes.c_size_t,
+                                  # the tree
+                                  c_u8p, ctypes.c_void_p, c_u32p, c_u64p, c_u64p, ctypes.c_void_p,
+                                  c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_uint32, ctypes.c_size_t,
+                                  # the keys and the mode
+                                  c_u8p, c_u64p, ctypes.c_uint64, ctypes.c_int,
+                                  # outputs
+                                  ctypes.c_void_p, ctypes.c_void_p, c_u32p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "lsm_decode_sst_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32]),
     "lsm_decode_sst": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u64p, c_u64p, ctypes.c_uint32,
                                       c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

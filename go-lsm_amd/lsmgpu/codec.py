@@ -1207,6 +1207,129 @@ def memtable_order(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, wal_off: 
     return mo
 
 
+# ---- memtable search and database.Get (lsm_memtable_search, lsm_db_get) -----------
+
+MEM_MISS, MEM_VALUE, MEM_DELETED = 0, 1, 2        # enum lsm_mem_result
+DBGET_EXACT, DBGET_TOMBSTONE_HIDES = 0, 1         # enum lsm_db_get_mode
+SRC_NONE, SRC_MEMTABLE, SRC_SSTABLE = -1, 0, 1    # enum lsm_get_source
+
+
+def memtable_search_index(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder,
+                          index: Optional[torch.Tensor] = None, stream=None) -> Optional[torch.Tensor]:
+    """lsm_memtable_search_index_build over the MEMTABLE_ALL order mo of the
+    replay r: each node's first 16 key bytes in mo.idx order.  Valid while
+    mo.idx is; pass `index` to rebuild into the same buffer.  None when there
+    is nothing to index (no logs or no slots): the search takes None."""
+    if mo.nlog == 0 or mo.nslot == 0:
+        return None
+    if index is None:
+        n = int(ctx.lib.lsm_memtable_search_index_bytes(mo.nslot))
+        index = torch.empty(n, dtype=torch.uint8, device=ctx.torch_device)
+    _lib.check(ctx.lib.lsm_memtable_search_index_build(
+        ctx.handle, _ptr(d_wal), _ptr(r.desc), _ptr(mo.idx), _ptr(mo.file_start), mo.nlog, mo.nslot,
+        _ptr(index), index.numel(), _stream_handle(stream)), "lsm_memtable_search_index_build")
+    return index
+
+
+def memtable_search_into(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder,
+                         batch: "RecordBatch", mem_result: torch.Tensor, log: torch.Tensor,
+                         slot: torch.Tensor, value: torch.Tensor, index: Optional[torch.Tensor] = None,
+                         stream=None) -> None:
+    """lsm_memtable_search: memtable.Manager.Search (memtable/manager.go:61-74)
+    of every key of `batch` over the memtables of mo (logs oldest first, the
+    newest searched first).  mem_result / log int32 and slot int32 (0xFFFFFFFF
+    reads as -1) per key, value int32[nkeys, 4] (a view into d_wal)."""
+    _lib.check(ctx.lib.lsm_memtable_search(
+        ctx.handle, _ptr(d_wal), _ptr(r.desc), _ptr(mo.idx), _ptr(mo.file_start), mo.nlog,
+        _ptr(index) if index is not None else None, index.numel() if index is not None else 0,
+        _ptr(batch.keys), _ptr(batch.koff), batch.n, _ptr(mem_result), _ptr(log), _ptr(slot), _ptr(value),
+        _stream_handle(stream)), "lsm_memtable_search")
+
+
+def memtable_search(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder,
+                    batch: "RecordBatch", index: Optional[torch.Tensor] = None, stream=None):
+    """-> (mem_result int32[nkeys], log int32[nkeys], slot int32[nkeys],
+    value int32[nkeys, 4]) on the device."""
+    dev = ctx.torch_device
+    n = max(batch.n, 1)
+    mem_result = torch.empty(n, dtype=torch.int32, device=dev)
+    log = torch.empty(n, dtype=torch.int32, device=dev)
+    slot = torch.empty(n, dtype=torch.int32, device=dev)
+    value = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    if batch.n:
+        memtable_search_into(ctx, d_wal, r, mo, batch, mem_result, log, slot, value, index=index,
+                             stream=stream)
+    return mem_result[:batch.n], log[:batch.n], slot[:batch.n], value[:batch.n]
+
+
+@dataclass
+class DbGet:
+    """lsm_db_get's per-key outputs on the device."""
+    mem_result: torch.Tensor  # int32: MEM_*
+    log: torch.Tensor         # int32
+    slot: torch.Tensor        # int32 (0xFFFFFFFF reads as -1)
+    level: torch.Tensor       # int32
+    table: torch.Tensor       # int32
+    result: torch.Tensor      # int32: GET_*
+    value: torch.Tensor       # int32[nkeys, 4]: the returned value's view
+    src: torch.Tensor         # int32: SRC_*
+
+
+def alloc_db_get(ctx: Context, nkeys: int) -> DbGet:
+    dev = ctx.torch_device
+    n = max(nkeys, 1)
+    i32 = lambda: torch.empty(n, dtype=torch.int32, device=dev)  # noqa: E731
+    return DbGet(i32(), i32(), i32(), i32(), i32(), i32(),
+                 torch.empty((n, 4), dtype=torch.int32, device=dev), i32())
+
+
+def db_get_into(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder,
+                d_img: torch.Tensor, sd: SstDecode, level_start, batch: "RecordBatch",
+                index: torch.Tensor, out: DbGet, mode: int = DBGET_TOMBSTONE_HIDES,
+                mem_index: Optional[torch.Tensor] = None, tree: Optional[SeekTree] = None,
+                ws: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lsm_db_get: database.Get (database/database.go:24-40) of every key of
+    `batch` -- the memtables of mo (memtable_search_into's arguments), then the
+    tree decoded into sd (search_into's arguments) for the keys they did not
+    answer.  index = level_index over sd; mem_index = memtable_search_index."""
+    ls = _level_start(level_start)
+    if int(ls[-1]) != sd.nfile:
+        raise ValueError(f"level_start ends at {int(ls[-1])}, the tree holds {sd.nfile} tables")
+    if ws is None:
+        ws = search_workspace(ctx, ls, batch.n)
+    nf = sd.nfile
+    _lib.check(ctx.lib.lsm_db_get(
+        ctx.handle, _ptr(d_wal), _ptr(r.desc), _ptr(mo.idx), _ptr(mo.file_start), mo.nlog,
+        _ptr(mem_index) if mem_index is not None else None,
+        mem_index.numel() if mem_index is not None else 0,
+        _ptr(d_img) if nf else None, _ptr(index) if nf else None, ls.ctypes.data,
+        _ptr(sd.d_file_off) if nf else None, _ptr(sd.d_file_len) if nf else None,
+        _ptr(sd.meta) if nf else None, None, _ptr(sd.idx_desc) if nf else None,
+        _ptr(sd.idx_value) if nf else None,
+        _ptr(tree.data) if tree is not None else None, tree.max_nidx if tree is not None else 0,
+        tree.data.numel() if tree is not None else 0,
+        _ptr(batch.keys), _ptr(batch.koff), batch.n, mode,
+        _ptr(out.mem_result), _ptr(out.log), _ptr(out.slot), _ptr(out.level), _ptr(out.table),
+        _ptr(out.result), _ptr(out.value), _ptr(out.src), _ptr(ws), ws.numel(), _stream_handle(stream)),
+        "lsm_db_get")
+
+
+def db_get(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder, d_img: torch.Tensor,
+           sd: SstDecode, level_start, batch: "RecordBatch", mode: int = DBGET_TOMBSTONE_HIDES,
+           index: Optional[torch.Tensor] = None, mem_index: Optional[torch.Tensor] = None,
+           tree: Optional[SeekTree] = None, stream=None) -> DbGet:
+    """-> DbGet of device tensors, each cut to nkeys entries."""
+    out = alloc_db_get(ctx, batch.n)
+    if index is None and sd.nfile:
+        index = level_index(ctx, d_img, sd, stream=stream)
+    if batch.n:
+        db_get_into(ctx, d_wal, r, mo, d_img, sd, level_start, batch, index, out, mode=mode,
+                    mem_index=mem_index, tree=tree, stream=stream)
+    n = batch.n
+    return DbGet(out.mem_result[:n], out.log[:n], out.slot[:n], out.level[:n], out.table[:n],
+                 out.result[:n], out.value[:n], out.src[:n])
+
+
 @dataclass
 class MemtableFlush:
     """memtable_flush's result: image f is out[file_off[f]:file_off[f] +

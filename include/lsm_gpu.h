@@ -53,7 +53,10 @@ extern "C" {
  * Added within v7 (backward compatible, the version stays 7; a binding finds
  * them by symbol lookup): lsm_search and lsm_search_workspace_bytes
  * (Manager.Search over a whole tree in one call); lsm_memtable_order and
- * lsm_memtable_order_workspace_bytes (a memtable's contents from its WAL). */
+ * lsm_memtable_order_workspace_bytes (a memtable's contents from its WAL);
+ * lsm_memtable_search with lsm_memtable_search_index_bytes / _index_build
+ * (memtable.Manager.Search over those memtables) and lsm_db_get with
+ * lsm_db_get_workspace_bytes (database.Get in one call). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -308,6 +311,89 @@ int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc 
                        uint32_t max_log_records, int scan, uint32_t *d_idx, uint64_t *d_file_start,
                        uint64_t *d_counts, void *d_ws, size_t ws_bytes, void *stream);
 
+/* ---- memtable search and database.Get (added within ABI 7) ----------------- */
+
+/* Batched memtable.Manager.Search (memtable/manager.go:61-74) over the
+ * memtables lsm_memtable_order delivers: the first half of database.Get
+ * (database/database.go:24-40).  SkipList.Search (skiplist/skiplist.go:60-79)
+ * finds the node with exactly the key: no node is (nil, false), a node whose
+ * value IsDeleted (exactly the 13 bytes of kv.DeletedValue, kv.go:29-43) is
+ * (nil, true), any other node (value, true).  Manager.Search asks Mem, then
+ * IMems from the last to the first; the first table with ok == true ends the
+ * search, also when what it returns is nil: a tombstone in a newer memtable
+ * hides a value in an older one.  Manager.Recover (manager.go:140-180) lists
+ * the WALs by ascending id, the last one becomes Mem, so for logs given OLDEST
+ * FIRST the search visits log nlog - 1, nlog - 2, ..., 0.
+ *
+ * d_bytes / d_desc are lsm_memtable_order's inputs, d_idx / d_file_start its
+ * outputs with LSM_MEMTABLE_ALL: log w's nodes are d_idx[d_file_start[w] ..
+ * d_file_start[w + 1]), in key order.  A failed, empty or overflowed log has
+ * no nodes there and answers nothing.  The probe keys are CSR (d_keys,
+ * d_koff with nkeys + 1 entries) under the input-slack contract; they are
+ * compared in Go string order over any key length (a probe longer than
+ * 1 << 20 bytes, kv.go:84, equals no node).  Per key, for the first log
+ * searched that holds a node with exactly that key:
+ *   d_mem_result[i] = LSM_MEM_VALUE or LSM_MEM_DELETED, d_log[i] = that log,
+ *   d_slot[i] = the node's index in d_desc, d_value[i] = {rec_off = the offset
+ *   in d_bytes of the value's u32 length prefix (desc.rec_off + 4 + key_len),
+ *   key_len = 0, val_len} for LSM_MEM_VALUE -- lsm_level_get's view
+ *   convention -- and all zero for LSM_MEM_DELETED;
+ * when no log holds it: LSM_MEM_MISS, -1, 0xFFFFFFFF, all zero.
+ * nlog == 0 answers every key LSM_MEM_MISS.
+ *
+ * What the WAL alone can and cannot say:
+ *   - Empty values.  A replayed empty value is make([]byte, 0), non-nil: a
+ *     found value of length 0 (LSM_MEM_VALUE, val_len 0), and Get returns it.
+ *     A live Put(key, nil) holds Go's nil and falls through to the tables; the
+ *     WAL encodes both as an empty value and the library follows the replayed
+ *     form.
+ *   - Delete on a full memtable.  Live, when Manager.Delete meets a full
+ *     memtable the old memtable's node is unlinked and the new Mem holds the
+ *     tombstone; replayed, the old log ends in (key, "").  The newer log is
+ *     searched first in both cases, so the answer is the same while both logs
+ *     are passed.
+ *   - LSM_MEMTABLE_RANGESCAN's d_idx is a subset of the nodes: searching it is
+ *     not Manager.Search, and the call cannot detect it.  Pass the
+ *     LSM_MEMTABLE_ALL order.
+ *
+ * d_index (optional): lsm_memtable_search_index_build's buffer.  It holds each
+ * node's first 16 key bytes in d_idx order (behind a 256-byte header with the
+ * number of nodes indexed), so a bisection step is one 16-byte gather and the
+ * node is read only on a 16-byte tie; without it a step is three dependent
+ * loads (d_idx -> d_desc -> the key).  The answers are identical.  It is built
+ * once per set of memtables and valid while d_idx is; nnode_max >=
+ * d_file_start[nlog] (nslot always suffices; the count is read on the device).
+ * A log whose nodes pass the indexed count (an index built with a smaller
+ * nnode_max) is searched through d_idx.  lsm_memtable_search_index_bytes(0)
+ * = 0; the build with nlog == 0 or nnode_max == 0 returns 0.
+ *
+ * Argument checks, in this order, all before any launch: ctx == NULL ->
+ * LSM_EINVAL; nkeys == 0 -> 0; nlog > 65535 or a required pointer NULL ->
+ * LSM_EINVAL; d_index != NULL with index_bytes below
+ * lsm_memtable_search_index_bytes(1) (no index fits) -> LSM_ESPACE.  The search
+ * is not told nnode_max, so that is all it can refuse: an index passed with an
+ * index_bytes smaller than it was built with does not fail, it serves only the
+ * logs whose nodes lie inside index_bytes and the others take the slower walk
+ * through d_idx (same answers).  Pass the size the build was given.
+ * lsm_memtable_search_index_build's checks, in this order, all before its
+ * launch: ctx == NULL -> LSM_EINVAL; nlog == 0 or nnode_max == 0 -> 0 (nothing
+ * written); nlog > 65535, nnode_max >= 2^32 - 1 (slots are u32) or a NULL
+ * d_bytes / d_desc / d_idx / d_file_start -> LSM_EINVAL; d_index == NULL or
+ * index_bytes below lsm_memtable_search_index_bytes(nnode_max) -> LSM_ESPACE.
+ * One launch, one thread per key (grid-stride past 2,048 workgroups); no host
+ * synchronisation, no read-back, no device allocation, no workspace: both
+ * calls can be captured in a graph. */
+enum lsm_mem_result { LSM_MEM_MISS = 0, LSM_MEM_VALUE = 1, LSM_MEM_DELETED = 2 };
+size_t lsm_memtable_search_index_bytes(uint64_t nnode_max);
+int lsm_memtable_search_index_build(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                                    const uint32_t *d_idx, const uint64_t *d_file_start, uint32_t nlog,
+                                    uint64_t nnode_max, void *d_index, size_t index_bytes, void *stream);
+int lsm_memtable_search(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
+                        const uint32_t *d_idx, const uint64_t *d_file_start, uint32_t nlog,
+                        const void *d_index, size_t index_bytes, const uint8_t *d_keys,
+                        const uint64_t *d_koff, uint64_t nkeys, int32_t *d_mem_result, int32_t *d_log,
+                        uint32_t *d_slot, lsm_rec_desc *d_value, void *stream);
+
 /* ---- whole .sst files ------------------------------------------------------ */
 
 /* Per-file result of lsm_decode_sst.  Offsets are relative to the file image. */
@@ -524,6 +610,53 @@ int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
                const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys,
                int32_t *d_level, int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value,
                const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
+               void *d_workspace, size_t ws_bytes, void *stream);
+
+/* database.Get (database/database.go:24-40) of nkeys keys in one asynchronous
+ * call: lsm_memtable_search over the memtables (its arguments, d_mem_index /
+ * mem_index_bytes being its d_index / index_bytes), then lsm_search (its
+ * arguments) for the keys the memtables did not answer.
+ *   LSM_DBGET_EXACT: Get as written -- `if value != nil return value`, else
+ *     SSTables.Search.  A key goes on to the tables unless its memtable result
+ *     is LSM_MEM_VALUE: a key whose memtable answer is a tombstone is searched
+ *     in the tables and can come back with an older value, or with a table's
+ *     tombstone bytes as an ordinary value.  What go-lsm does today; exact in
+ *     the sense of LSM_TIE_GOHEAP and LSM_MEMTABLE_RANGESCAN.
+ *   LSM_DBGET_TOMBSTONE_HIDES: only LSM_MEM_MISS goes on.  A LSM_MEM_DELETED
+ *     key ends with d_src = LSM_SRC_MEMTABLE, d_result = LSM_GET_ABSENT and a
+ *     zero value.  The recommended mode.
+ * Any other mode returns LSM_EINVAL.
+ * d_mem_result / d_log / d_slot: lsm_memtable_search's, for every key.
+ * d_level / d_table / d_result: lsm_search's for the keys that went on, error
+ * codes included; -1, -1, LSM_GET_ABSENT for the others.  d_value[i] = the
+ * returned value's view and d_src[i] the buffer it points into:
+ * LSM_SRC_MEMTABLE (d_bytes), LSM_SRC_SSTABLE (d_img; also for a table's error
+ * code, with a zero view), LSM_SRC_NONE when Get returns (nil, nil).
+ * A key the memtables answered costs no table work (no hash, no filter test,
+ * no Seek): lsm_search's kernel, instantiated with the memtable result as a
+ * per-key input, skips it.  nlog == 0 reduces to lsm_search's answers, an
+ * empty tree to the memtables'.  Two launches; no host synchronisation, no
+ * read-back, no device allocation (capturable).  Checks: ctx == NULL or an
+ * unknown mode -> LSM_EINVAL; nkeys == 0 -> 0; then lsm_search's and
+ * lsm_memtable_search's.  Workspace: lsm_db_get_workspace_bytes (lsm_search's;
+ * LSM_ESPACE below it). */
+enum lsm_db_get_mode { LSM_DBGET_EXACT = 0, LSM_DBGET_TOMBSTONE_HIDES = 1 };
+enum lsm_get_source { LSM_SRC_NONE = -1, LSM_SRC_MEMTABLE = 0, LSM_SRC_SSTABLE = 1 };
+size_t lsm_db_get_workspace_bytes(const uint32_t *level_start, uint64_t nkeys);
+int lsm_db_get(lsm_ctx *ctx,
+               /* the memtables: lsm_memtable_search's inputs */
+               const uint8_t *d_bytes, const lsm_rec_desc *d_desc, const uint32_t *d_idx,
+               const uint64_t *d_file_start, uint32_t nlog, const void *d_mem_index,
+               size_t mem_index_bytes,
+               /* the tree: lsm_search's inputs */
+               const uint8_t *d_img, const void *d_index,
+               const uint32_t *level_start, /* HOST, LSM_SEARCH_LEVELS + 1 entries */
+               const uint64_t *d_file_off, const uint64_t *d_file_len, const lsm_sst_meta *d_meta,
+               const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value,
+               const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
+               const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys, int mode,
+               int32_t *d_mem_result, int32_t *d_log, uint32_t *d_slot, int32_t *d_level,
+               int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value, int32_t *d_src,
                void *d_workspace, size_t ws_bytes, void *stream);
 
 /* The Seek tree of a level for lsm_level_get, built once when the level is
