@@ -1,4 +1,4 @@
-// encode.hip — batched record encode, fused-bloom .sst build and bloom probe (gfx950).
+// encode.hip — batched record encode and fused-bloom .sst build (gfx950).
 //
 // Encoding is output-centric.  With a CSR record batch every record's output
 // position is closed-form (KV: 8*i + K(i) + V(i), V: 4*i + V(i), IDX:
@@ -19,6 +19,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "hashrec.h"
 #include "murmur.h"
 
 namespace lsm {
@@ -852,56 +853,11 @@ __global__ __launch_bounds__(1024) void bloom_file_kernel(BloomFileArgs a) {
 // 208 CUs with LDS to spare for only a few region waves.  For two-slice
 // filters with k <= 16 the build is split: the region writer (which gathers
 // every key into LDS for the index region anyway) hashes each key once and
-// leaves per key the residues mod m of the four location classes' bases and
-// of the class step of classes 0 and 3 (location(j) = h[j%2] + j*h[2 + ((j + j%2) % 4)/2],
-// bloom.go:133-136: class c = j%4 is an arithmetic progression) plus the carry
-// bit of each 64-bit step and the two carries that rebuild the other class
-// step from the class bases: 16 bytes; bloom_or_kernel then rebuilds the k
-// locations of every key of its filter from them (additions only) and ORs
-// those of its slice into LDS.
-//
-// Record (m <= 2^21: a two-slice filter is at most 2 * 819,200 bits), dword c
-// of 4: bits 0-20 the residue of class c's base, bits 21-23 the carries of
-// its three steps, bits 24-31 byte c of X = res(4 h2) | a << 21 | b << 22,
-// where T = 2 h3 mod 2^64, a = carry of h0 + T (class 2's base) and b = the
-// top bit of T: res(T) = res(base2) - res(base0) + a (2^64 mod m), and
-// res(4 h3) = 2 res(T) - b (2^64 mod m), all mod m.  (24 bytes per key, the
-// round-4 record, were read twice and written once: 1.28x the algorithmic
-// traffic of config 3.)
-constexpr uint32_t kHashRecDwords = 4;
-constexpr uint32_t kHashRecBits = 21;  // residue bits: m <= 2^21
+// leaves per key its 16-byte hash record (hashrec.h: store_hash_rec, the
+// record's layout); bloom_or_kernel then rebuilds the k locations of every
+// key of its filter from them (additions only) and ORs those of its slice
+// into LDS.
 constexpr uint32_t kOrSlices = 2;  // bloom_or_kernel workgroups per filter
-constexpr uint32_t kSplitMaxK = 16;  // three carries per class fit the record
-
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-// The 16-byte hash record of a key from its sum256 digest (layout above).
-__device__ __forceinline__ void store_hash_rec(const uint64_t h[4], uint32_t m, uint32_t rl,
-                                               uint32_t rh, uint32_t *rec) {
-    const uint64_t T = h[3] << 1;
-    const uint64_t loc[4] = {h[0], h[1] + h[3], h[0] + T, h[1] + h[2] + (h[2] << 1)};
-    const uint64_t st2 = h[2] << 2, st3 = h[3] << 2;
-    uint32_t r[4];
-#pragma unroll
-    for (uint32_t c = 0; c < 4; c++) {
-        uint32_t cy = 0;  // bit n: the step to location 4(n + 1) + c carries
-        const uint64_t st = (c == 0 || c == 3) ? st2 : st3;
-        uint64_t l = loc[c];
-#pragma unroll
-        for (uint32_t n = 0; n < 3; n++) {
-            uint64_t nl;
-            cy |= (uint32_t)__builtin_add_overflow(l, st, &nl) << n;
-            l = nl;
-        }
-        r[c] = mod_small(loc[c], m, rl, rh) | cy << kHashRecBits;
-    }
-    const uint32_t a = loc[2] < h[0];  // h0 + T wrapped
-    const uint32_t x = mod_small(st2, m, rl, rh) | a << 21 | (uint32_t)(T >> 63) << 22;
-#pragma unroll
-    for (uint32_t c = 0; c < 3; c++) r[c] |= ((x >> (8 * c)) & 0xFFu) << 24;
-    *(gptr_t<u32x4>)gbl(rec) = u32x4{r[0], r[1], r[2], r[3]};
-}
 
 struct BloomOrArgs {
     const uint64_t *file_start;  // rec[0] is key file_start[0]
@@ -2080,53 +2036,6 @@ __global__ __launch_bounds__(64) void sst_meta_kernel(SstArgs a) { sst_meta_body
 //    loses 2^64: its residue less 2^64 mod m), by bitfield insert.
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 
-// A hash record (store_hash_rec) unpacked: the residues of the four class
-// bases (location c of class c) and each class's three steps, the carried
-// ones already less 2^64 mod m: location 4(n + 1) + c = r[c] + st[c][n] mod m.
-struct HashRecSteps {
-    uint32_t r[4];
-    uint32_t st[4][3];
-};
-
-__device__ __forceinline__ HashRecSteps unpack_hash_rec(const u32x4 x, uint32_t m, uint32_t c64) {
-    constexpr uint32_t kRes = (1u << kHashRecBits) - 1;
-    const uint32_t raw[4] = {x.x, x.y, x.z, x.w};
-    HashRecSteps H;
-#pragma unroll
-    for (uint32_t c = 0; c < 4; c++) H.r[c] = raw[c] & kRes;
-    // X = res(4 h2) | a << 21 | b << 22 from the top bytes of dwords 0-2
-    const uint32_t X = __builtin_amdgcn_perm(raw[1], raw[0], 0x0c0c0703u) |
-                       (raw[2] >> 24) << 16;
-    const uint32_t d2 = X & kRes;
-    // res(T) = res(base2) - res(base0) + a c64, res(4 h3) = 2 res(T) - b c64 (mod m)
-    uint32_t rt = H.r[2] - H.r[0];
-    rt = min(rt, rt + m);
-    rt = (X >> 21) & 1 ? rt + c64 : rt;
-    rt = min(rt, rt - m);
-    uint32_t d3 = rt << 1;
-    d3 = min(d3, d3 - m);
-    d3 = (X >> 22) & 1 ? d3 - c64 : d3;
-    d3 = min(d3, d3 + m);
-    // the steps less 2^64 mod m, for a step whose 64-bit add wraps
-    const uint32_t t2 = d2 - c64, t3 = d3 - c64;
-    const uint32_t w2 = min(t2, t2 + m), w3 = min(t3, t3 + m);
-#pragma unroll
-    for (uint32_t c = 0; c < 4; c++) {
-        const bool a2 = c == 0 || c == 3;
-#pragma unroll
-        for (uint32_t n = 0; n < 3; n++) {
-            // all-ones where the step from location 4n + c carries (bit
-            // 21 + n of dword c), then one bitfield insert (the compiler's
-            // and / compare / cndmask form is three VALU)
-            const uint32_t msk = (uint32_t)__builtin_amdgcn_sbfe((int)raw[c], kHashRecBits + n, 1);
-            uint32_t v;
-            __asm__("v_bfi_b32 %0, %1, %2, %3" : "=v"(v) : "v"(msk), "v"(a2 ? w2 : w3), "v"(a2 ? d2 : d3));
-            H.st[c][n] = v;
-        }
-    }
-    return H;
-}
-
 template <uint32_t K, bool Masked>
 __device__ __forceinline__ void or_key_locations(const u32x4 x, uint32_t k, uint32_t m, uint32_t c64,
                                                  uint32_t base, uint32_t lo, uint32_t span) {
@@ -2219,7 +2128,7 @@ __global__ __launch_bounds__(1024) void bloom_or_kernel(BloomOrArgs a, SstArgs s
 
 
 
-// ---- probe / hash ----------------------------------------------------------
+// ---- hash ------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void sum256_kernel(const uint8_t *keys, const uint64_t *koff,
                                                      uint64_t n, uint64_t *out) {
@@ -2229,1422 +2138,6 @@ __global__ __launch_bounds__(256) void sum256_kernel(const uint8_t *keys, const 
     uint64_t k0 = koff[i];
     sum256(keys + k0, koff[i + 1] - k0, h);
     for (int j = 0; j < 4; j++) out[4 * i + j] = h[j];
-}
-
-__global__ __launch_bounds__(256) void bloom_probe_kernel(const uint64_t *words, uint64_t m,
-                                                          uint64_t mrecip, uint32_t k,
-                                                          const uint8_t *keys,
-                                                          const uint64_t *koff, uint64_t n,
-                                                          uint8_t *hit) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint64_t h[4];
-    uint64_t k0 = koff[i];
-    sum256(keys + k0, koff[i + 1] - k0, h);
-    uint8_t ok = 1;
-    for (uint32_t j = 0; j < k && ok; j++) {
-        uint64_t p = mod_barrett(location(h[0], h[1], h[2], h[3], j), m, mrecip);
-        if (!((words[p >> 6] >> (p & 63)) & 1)) ok = 0;
-    }
-    hit[i] = ok;
-}
-
-// ---- batched SSTable.MayContain ------------------------
-//
-// d_hit[i * nfile + f] = SSTable.MayContain(key i) on file f (sstable.go:300-
-// 305): the key range check against the header's min / max key in Go string
-// order, then Filter.Test (bloom.go:371-379) on the filter block as stored in
-// the image (u64 big-endian words, bitset v1.22.0 WriteTo; bit p -> word p>>6
-// bit p&63; bitset.Test is false past its length).  One thread per key
-// hashes it once (sum256) and walks the files.  Per tile of kMcTile files the
-// block stages each file's bounds (16-byte big-endian prefixes), pointers
-// and filter parameters in LDS, packs its results four files to a dword in
-// an LDS out tile, and then writes the block's rows x tile sub-block of the
-// hit matrix coalesced (dwords when nfile is a multiple of 4).
-constexpr uint32_t kMcTile = 64;
-constexpr uint32_t kMcThreads = 256;
-constexpr uint32_t kMcProbeGrid = 1024;  // per-probe path: workgroups (grid-stride)
-constexpr uint32_t kMcRow = kMcTile / 4 + 1;  // dwords per out-tile row (+1: LDS banks)
-
-// Filter.Test tests hashNum locations and stops at the first clear bit; a
-// stored k beyond this (only a corrupted file) is capped so a probe of a
-// saturated filter ends (deviations).
-constexpr uint32_t kMcMaxK = 1u << 24;
-
-struct McFile {
-    uint32_t lo[4], hi[4];  // first 16 bytes of min / max key, big-endian, zero padded
-    uint32_t lo_len, hi_len;
-    uint32_t ok;            // header and filter decoded (lsm_sst_meta.stage not 1 or 2)
-    uint32_t k;             // filter k, capped so a probe always ends
-    uint64_t lo_at, hi_at;  // image offsets of the min / max key bytes
-    uint64_t words_at;      // image offset of the first filter word
-    uint64_t m, mr, nbits;  // filter m, its Barrett reciprocal, stored bit count
-};
-
-__device__ __forceinline__ uint32_t be_word_at(const uint8_t *p, uint64_t len, uint32_t j) {
-    uint32_t w = 0;
-    for (uint32_t b = 0; b < 4; b++) {
-        const uint64_t at = 4ull * j + b;
-        w = (w << 8) | (at < len ? p[at] : 0u);
-    }
-    return w;
-}
-
-// Go string comparison of a and b (bytewise, then length): <0, 0, >0.
-__device__ __forceinline__ int go_cmp(const uint8_t *a, uint64_t la, const uint8_t *b,
-                                      uint64_t lb) {
-    const uint64_t n = la < lb ? la : lb;
-    for (uint64_t i = 0; i < n; i++)
-        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
-    return la < lb ? -1 : la > lb ? 1 : 0;
-}
-
-// Compare the 16-byte big-endian prefixes, then (when both go on) the bytes.
-__device__ __forceinline__ int bound_cmp(const uint32_t bw[4], uint64_t blen, const uint8_t *bp,
-                                         const uint32_t kw[4], uint64_t klen, const uint8_t *kp) {
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-        if (bw[j] != kw[j]) return bw[j] < kw[j] ? -1 : 1;
-    // equal over min(16, len) bytes with zero padding: decide by the rest
-    if (blen <= 16 || klen <= 16) {
-        // zero padding hides a real 0x00 byte only when one side ends first
-        return go_cmp(bp, blen, kp, klen);
-    }
-    return go_cmp(bp + 16, blen - 16, kp + 16, klen - 16);
-}
-
-// Lexicographic compare of two 16-byte big-endian prefixes: -1, 0, 1 (branch-free).
-__device__ __forceinline__ int prefix_cmp(const uint32_t a[4], const uint32_t b[4]) {
-    const uint64_t a0 = (uint64_t)a[0] << 32 | a[1], a1 = (uint64_t)a[2] << 32 | a[3];
-    const uint64_t b0 = (uint64_t)b[0] << 32 | b[1], b1 = (uint64_t)b[2] << 32 | b[3];
-    const int lt = (a0 < b0) | ((a0 == b0) & (a1 < b1));
-    const int gt = (a0 > b0) | ((a0 == b0) & (a1 > b1));
-    return gt - lt;
-}
-
-// bound_cmp with the common case (prefixes differ) branch-free
-__device__ __forceinline__ int bound_cmp_fast(const uint32_t bw[4], uint64_t blen, const uint8_t *bp,
-                                              const uint32_t kw[4], uint64_t klen, const uint8_t *kp) {
-    const int c = prefix_cmp(bw, kw);
-    if (c != 0) return c;
-    return bound_cmp(bw, blen, bp, kw, klen, kp);
-}
-
-__global__ __launch_bounds__(kMcThreads) void may_contain_kernel(const uint8_t *img,
-                                                                 const uint64_t *file_off,
-                                                                 const lsm_sst_meta *meta,
-                                                                 uint32_t nfile, const uint8_t *keys,
-                                                                 const uint64_t *koff, uint64_t nkeys,
-                                                                 uint8_t *hit,
-                                                                 const uint32_t *grouped) {
-    __shared__ McFile tile[kMcTile];
-    if (*grouped) return;  // the files are sorted and disjoint: mc_* kernels answer
-    __shared__ uint32_t sout[kMcThreads * kMcRow];
-    // a capped grid strides over the probes (when the grouped path answers,
-    // fewer workgroups have to start only to see the flag)
-    for (uint64_t i0 = (uint64_t)blockIdx.x * kMcThreads; i0 < nkeys;
-         i0 += (uint64_t)gridDim.x * kMcThreads) {
-        __syncthreads();  // sout and tile of the previous rows are consumed
-        const uint64_t i = i0 + threadIdx.x;
-        const bool act = i < nkeys;
-        const uint32_t rows = nkeys - i0 < kMcThreads ? (uint32_t)(nkeys - i0) : kMcThreads;
-        uint64_t k0 = 0, kl = 0;
-        uint64_t h[4] = {0, 0, 0, 0};
-        uint32_t kw[4] = {0, 0, 0, 0};
-        if (act) {
-            k0 = koff[i];
-            kl = koff[i + 1] - k0;
-            sum256(keys + k0, kl, h);
-    #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) kw[j] = be_word_at(keys + k0, kl, j);
-        }
-        const uint8_t *kp = keys + k0;
-        for (uint32_t f0 = 0; f0 < nfile; f0 += kMcTile) {
-            const uint32_t nt = nfile - f0 < kMcTile ? nfile - f0 : kMcTile;
-            __syncthreads();
-            for (uint32_t t = threadIdx.x; t < nt; t += kMcThreads) {
-                const lsm_sst_meta &M = meta[f0 + t];
-                const uint64_t fo = file_off[f0 + t];
-                const uint8_t *base = img + fo;
-                McFile F;
-                F.ok = M.stage != 1 && M.stage != 2;
-                F.lo_len = (uint32_t)M.min_key_len;
-                F.hi_len = (uint32_t)M.max_key_len;
-                for (uint32_t j = 0; j < 4; j++) {
-                    F.lo[j] = F.ok ? be_word_at(base + M.min_key_off, M.min_key_len, j) : 0;
-                    F.hi[j] = F.ok ? be_word_at(base + M.max_key_off, M.max_key_len, j) : 0;
-                }
-                F.lo_at = fo + M.min_key_off;
-                F.hi_at = fo + M.max_key_off;
-                F.words_at = fo + M.filter_words_off;
-                // k from the file (no max(1, k) on a decoded filter); Test's
-                // early exit ends a probe at its first clear bit, a corrupted k
-                // beyond kMcMaxK is capped (deviations)
-                F.k = M.filter_k < kMcMaxK ? (uint32_t)M.filter_k : kMcMaxK;
-                F.m = M.filter_m;
-                F.mr = M.filter_m ? ~0ull / M.filter_m : 0;
-                F.nbits = M.filter_nbits;
-                tile[t] = F;
-            }
-            // a tile of decoded files in key order with disjoint ranges (level >= 1
-            // files) holds a key in at most one file: the last whose MinKey <= key
-            bool sorted = true;
-            if (threadIdx.x < nt) {
-                const McFile &A = tile[threadIdx.x];
-                // MinKey <= MaxKey too: a corrupted header with min > max breaks
-                // the order the binary search relies on
-                sorted = A.ok != 0 &&
-                         bound_cmp_fast(A.lo, A.lo_len, img + A.lo_at, A.hi, A.hi_len, img + A.hi_at) <= 0;
-                if (sorted && threadIdx.x + 1 < nt) {
-                    const McFile &B = tile[threadIdx.x + 1];
-                    sorted = B.ok && bound_cmp_fast(A.hi, A.hi_len, img + A.hi_at, B.lo, B.lo_len,
-                                                    img + B.lo_at) < 0;
-                }
-            }
-            sorted = __syncthreads_and(sorted);
-            uint32_t cand_lo = 0, cand_hi = nt;  // files to test: [cand_lo, cand_hi)
-            if (sorted && act) {
-                uint32_t lo = 0, hi = nt;  // first t with MinKey > key
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) / 2;
-                    const McFile &F = tile[mid];
-                    if (bound_cmp_fast(F.lo, F.lo_len, img + F.lo_at, kw, kl, kp) <= 0) lo = mid + 1;
-                    else hi = mid;
-                }
-                cand_lo = lo ? lo - 1 : 0;
-                cand_hi = lo;
-            }
-            uint32_t pack = 0;
-            for (uint32_t t = 0; t < nt; t++) {
-                uint32_t r = 0;
-                if (act && t >= cand_lo && t < cand_hi && tile[t].ok) {
-                    const McFile &F = tile[t];
-                    // sstable.go:301: MinKey > key || MaxKey < key -> false
-                    if (bound_cmp_fast(F.lo, F.lo_len, img + F.lo_at, kw, kl, kp) <= 0 &&
-                        bound_cmp_fast(F.hi, F.hi_len, img + F.hi_at, kw, kl, kp) >= 0) {
-                        const uint64_t m = F.m;
-                        // hashNum 0: Test is true (bloom.go:373 loop never runs);
-                        // m == 0 with k > 0: Go's location() divides by zero and
-                        // panics, answered false here
-                        r = F.k == 0 || m != 0;
-                        // Test's answer is the AND of all k bits (its early exit
-                        // changes nothing): sixteen loads in flight at a time
-                        for (uint32_t j0 = 0; j0 < F.k && r; j0 += 16) {
-                            uint32_t bits = 1;
-    #pragma unroll
-                            for (uint32_t u = 0; u < 16; u++) {
-                                const uint32_t j = j0 + u;
-                                if (j < F.k && r) {
-                                    const uint64_t x = location(h[0], h[1], h[2], h[3], j);
-                                    const uint64_t p = m < (1ull << 63) ? mod_barrett(x, m, F.mr) : x % m;
-                                    bits &= p < F.nbits
-                                                ? (uint32_t)(img[F.words_at + 8 * (p >> 6) + 7 - ((p & 63) >> 3)] >> (p & 7)) & 1
-                                                : 0u;
-                                }
-                            }
-                            r &= bits;
-                        }
-                    }
-                }
-                pack |= r << (8 * (t & 3));
-                if ((t & 3) == 3 || t + 1 == nt) {
-                    sout[threadIdx.x * kMcRow + t / 4] = pack;
-                    pack = 0;
-                }
-            }
-            __syncthreads();
-            // the rows x nt sub-block of hit, coalesced
-            if ((nfile & 3) == 0) {  // every row segment starts 4-aligned (nt is a multiple of 4)
-                const uint32_t nd = nt / 4;
-                for (uint32_t x = threadIdx.x; x < rows * nd; x += kMcThreads) {
-                    const uint32_t rr = x / nd, c = x % nd;
-                    *reinterpret_cast<uint32_t *>(hit + (i0 + rr) * nfile + f0 + 4 * c) =
-                        sout[rr * kMcRow + c];
-                }
-            } else {
-                for (uint32_t x = threadIdx.x; x < rows * nt; x += kMcThreads) {
-                    const uint32_t rr = x / nt, c = x % nt;
-                    hit[(i0 + rr) * nfile + f0 + c] = (uint8_t)(sout[rr * kMcRow + c / 4] >> (8 * (c & 3)));
-                }
-            }
-        }
-    }
-}
-
-// Grouped path for the level >= 1 shape (every file decoded, files in key
-// order with disjoint ranges, at most kMcMaxFiles files): each probe has at
-// most one candidate file.  mc_classify_kernel hashes the candidates once and
-// groups each workgroup's by file into its slots (the level search's layout,
-// LvWs), and lv_test_kernel<true> (one workgroup per file) stages the filter
-// in LDS and tests its probes' bits there: the filter bits are read once from
-// HBM instead of once per probe bit.
-constexpr uint32_t kMcLdsBytes = 144 * 1024;  // filter words staged in LDS per file
-constexpr uint32_t kMcNone = 0xFFFFFFFFu;
-constexpr uint32_t kMcGroupThreads = 1024;
-constexpr uint32_t kMcGroupPer = 2;  // probes per thread
-constexpr uint32_t kMcGroupProbes = kMcGroupThreads * kMcGroupPer;
-constexpr uint32_t kMcMaxFiles = 2048;  // LDS bounds + counters; more files: per-probe path
-
-// A table whose filter takes the 16-byte hash record of the encode path
-// (store_hash_rec: m <= 2^21, k <= 16; go-lsm's 1.6 Mbit, k = 16): classify
-// stores the record for the table's m, and the test rebuilds the locations
-// from it by additions -- 16 bytes per probe through the workspace instead
-// of the 32-byte sum256, and no modulo in the test.
-__device__ __forceinline__ bool lv_compact(const McFile &F) {
-    return F.m != 0 && F.m <= (1ull << kHashRecBits) && F.k <= kSplitMaxK;
-}
-
-constexpr uint32_t kLvThreads = 1024;
-constexpr uint32_t kLvPer = 2;  // probes per thread
-constexpr uint32_t kLvProbes = kLvThreads * kLvPer;
-constexpr uint32_t kLvMaxFiles = 2048;
-constexpr uint32_t kLvMaxWgs = 1024;  // classify workgroups per pass (2M probes)
-
-struct LvWs {
-    McFile *files;
-    uint32_t *grid;   // [nfile][nwg]: the table's first slot in the workgroup
-    uint32_t *cnt;    // [nfile][nwg]: the table's probes in the workgroup
-    uint32_t *ids;    // [nwg * 2048] probe of each slot
-    u32x4 *rec;       // [nwg * 2048] its 16-byte hash record (lv_compact tables),
-                      // else h0, h1 of its sum256
-    u32x4 *ext;       // [nwg * 2048] h2, h3 (tables that are not lv_compact)
-};
-
-
-LvWs lv_ws_layout(uint8_t *base, uint32_t nfile, uint64_t nkeys, size_t *total) {
-    LvWs w{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + at : nullptr;
-        at += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
-    const uint64_t pass = nkeys < (uint64_t)kLvMaxWgs * kLvProbes ? nkeys : (uint64_t)kLvMaxWgs * kLvProbes;
-    const uint64_t nwg = (pass + kLvProbes - 1) / kLvProbes;
-    const size_t nf = nfile ? nfile : 1;
-    w.files = reinterpret_cast<McFile *>(take(sizeof(McFile) * nf));
-    w.grid = reinterpret_cast<uint32_t *>(take(4 * nf * (nwg ? nwg : 1)));
-    w.cnt = reinterpret_cast<uint32_t *>(take(4 * nf * (nwg ? nwg : 1)));
-    w.ids = reinterpret_cast<uint32_t *>(take(4 * (nwg ? nwg : 1) * kLvProbes));
-    w.rec = reinterpret_cast<u32x4 *>(take(16 * (nwg ? nwg : 1) * kLvProbes));
-    w.ext = reinterpret_cast<u32x4 *>(take(16 * (nwg ? nwg : 1) * kLvProbes));
-    if (total) *total = at;
-    return w;
-}
-
-static_assert(kMcGroupProbes == kLvProbes && kMcGroupThreads == kLvThreads && kMcMaxFiles == kLvMaxFiles,
-              "the all-tables classify fills the level search's slot layout");
-
-struct McWs {
-    uint32_t *flag;     // [0] = 1: grouped path
-    McFile *files;
-    LvWs lv;            // the probes grouped by candidate file, as the level search's
-};
-
-// key bytes [p, p + len) as four big-endian words, zero padded past len
-// (reads 16 bytes at p: the input slack covers a key that ends a buffer)
-__device__ __forceinline__ void key_prefix(const uint8_t *p, uint64_t len, uint32_t kw[4]) {
-    uint64_t f0 = ldg_u64_unaligned(p), f1 = ldg_u64_unaligned(p + 8);
-    if (len < 8) { f0 &= len ? (~0ull >> (64 - 8 * len)) : 0; f1 = 0; }
-    else if (len < 16) f1 &= len > 8 ? (~0ull >> (128 - 8 * len)) : 0;
-    kw[0] = __builtin_bswap32((uint32_t)f0);
-    kw[1] = __builtin_bswap32((uint32_t)(f0 >> 32));
-    kw[2] = __builtin_bswap32((uint32_t)f1);
-    kw[3] = __builtin_bswap32((uint32_t)(f1 >> 32));
-}
-
-__device__ __forceinline__ McFile mc_file(const uint8_t *img, const uint64_t *file_off,
-                                          const lsm_sst_meta &M, uint32_t f) {
-    const uint64_t fo = file_off[f];
-    const uint8_t *base = img + fo;
-    McFile F;
-    F.ok = M.stage != 1 && M.stage != 2;
-    F.lo_len = (uint32_t)M.min_key_len;
-    F.hi_len = (uint32_t)M.max_key_len;
-    // the key prefixes by unaligned 8-byte loads, all in flight (byte loads
-    // under a per-byte condition were 32 serialized round trips per file)
-    for (uint32_t j = 0; j < 4; j++) F.lo[j] = F.hi[j] = 0;
-    if (F.ok) {
-        key_prefix(base + M.min_key_off, M.min_key_len, F.lo);
-        key_prefix(base + M.max_key_off, M.max_key_len, F.hi);
-    }
-    F.lo_at = fo + M.min_key_off;
-    F.hi_at = fo + M.max_key_off;
-    F.words_at = fo + M.filter_words_off;
-    F.k = M.filter_k < kMcMaxK ? (uint32_t)M.filter_k : kMcMaxK;
-    F.m = M.filter_m;
-    F.mr = M.filter_m ? ~0ull / M.filter_m : 0;
-    F.nbits = M.filter_nbits;
-    return F;
-}
-
-__global__ __launch_bounds__(256) void mc_prep_kernel(const uint8_t *img, const uint64_t *file_off,
-                                                      const lsm_sst_meta *meta, uint32_t nfile,
-                                                      McWs w) {
-    bool ok = true;
-    for (uint32_t f = threadIdx.x; f < nfile; f += blockDim.x) {
-        const McFile F = mc_file(img, file_off, meta[f], f);
-        w.files[f] = F;
-        // m < 2^63 for the Barrett reduction; MinKey <= MaxKey (a corrupted
-        // header with min > max would break the order of the bound search)
-        ok = ok && F.ok && F.m < (1ull << 63) &&
-             bound_cmp_fast(F.lo, F.lo_len, img + F.lo_at, F.hi, F.hi_len, img + F.hi_at) <= 0;
-    }
-    if (nfile > kMcMaxFiles) ok = false;
-    __syncthreads();
-    for (uint32_t f = threadIdx.x; f + 1 < nfile; f += blockDim.x) {
-        const McFile &A = w.files[f], &B = w.files[f + 1];
-        ok = ok && bound_cmp_fast(A.hi, A.hi_len, img + A.hi_at, B.lo, B.lo_len, img + B.lo_at) < 0;
-    }
-    ok = __syncthreads_and(ok);
-    if (threadIdx.x == 0) w.flag[0] = ok ? 1u : 0u;
-}
-
-// Probes are grouped block-locally first (LDS counters), so each workgroup
-// adds to a file's global counter once: 1M probes over 208 files serialised
-// on 208 global atomics took 350 us, the block-local counts take a few.
-// The files' bound prefixes sit in LDS for the candidate search.
-__global__ __launch_bounds__(kMcGroupThreads) void mc_classify_kernel(const uint8_t *img, uint32_t nfile,
-                                                                      const uint8_t *keys,
-                                                                      const uint64_t *koff,
-                                                                      uint64_t k_begin, uint64_t nkeys,
-                                                                      McWs w, uint32_t nwg,
-                                                                      uint8_t *hit) {
-    __shared__ uint4 slo[kMcMaxFiles], shi[kMcMaxFiles];
-    __shared__ uint32_t lh[kMcMaxFiles];
-    __shared__ uint32_t part[kMcGroupThreads];
-    if (!w.flag[0]) return;
-    const uint32_t t = threadIdx.x;
-    for (uint32_t f = threadIdx.x; f < nfile; f += kMcGroupThreads) {
-        const McFile &F = w.files[f];
-        slo[f] = make_uint4(F.lo[0], F.lo[1], F.lo[2], F.lo[3]);
-        shi[f] = make_uint4(F.hi[0], F.hi[1], F.hi[2], F.hi[3]);
-        lh[f] = 0;
-    }
-    // every probe's first 16 key bytes (dword loads; batches are 16-byte
-    // padded), all loads in flight before the search
-    uint64_t k0[kMcGroupPer], kl[kMcGroupPer], f0[kMcGroupPer], f1[kMcGroupPer];
-#pragma unroll
-    for (uint32_t p = 0; p < kMcGroupPer; p++) {
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kMcGroupProbes + p * kMcGroupThreads + t;
-        k0[p] = i < nkeys ? koff[i] : 0;
-        kl[p] = i < nkeys ? koff[i + 1] - k0[p] : 0;
-    }
-#pragma unroll
-    for (uint32_t p = 0; p < kMcGroupPer; p++) {
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kMcGroupProbes + p * kMcGroupThreads + t;
-        f0[p] = i < nkeys ? ldg_u64_unaligned(keys + k0[p]) : 0;
-        f1[p] = i < nkeys ? ldg_u64_unaligned(keys + k0[p] + 8) : 0;
-    }
-    uint32_t kw[kMcGroupPer][4];
-#pragma unroll
-    for (uint32_t p = 0; p < kMcGroupPer; p++) {
-        // zero the bytes past the key, then the big-endian prefix words
-        const uint64_t l = kl[p];
-        if (l < 8) { f0[p] &= l ? (~0ull >> (64 - 8 * l)) : 0; f1[p] = 0; }
-        else if (l < 16) f1[p] &= l > 8 ? (~0ull >> (128 - 8 * l)) : 0;
-        kw[p][0] = __builtin_bswap32((uint32_t)f0[p]);
-        kw[p][1] = __builtin_bswap32((uint32_t)(f0[p] >> 32));
-        kw[p][2] = __builtin_bswap32((uint32_t)f1[p]);
-        kw[p][3] = __builtin_bswap32((uint32_t)(f1[p] >> 32));
-    }
-    __syncthreads();
-    uint32_t cand[kMcGroupPer], rank[kMcGroupPer];
-    uint64_t hh[kMcGroupPer][4];
-#pragma unroll
-    for (uint32_t p = 0; p < kMcGroupPer; p++) cand[p] = kMcNone;
-#pragma unroll
-    for (uint32_t p = 0; p < kMcGroupPer; p++) {
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kMcGroupProbes + p * kMcGroupThreads + t;
-        if (i >= nkeys) break;
-        const uint8_t *kp = keys + k0[p];
-        uint32_t lo = 0, hi = nfile;  // first file with MinKey > key
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) / 2;
-            const uint4 v = slo[mid];
-            const uint32_t bw[4] = {v.x, v.y, v.z, v.w};
-            int c = prefix_cmp(bw, kw[p]);
-            if (c == 0) {
-                const McFile &F = w.files[mid];
-                c = bound_cmp(bw, F.lo_len, img + F.lo_at, kw[p], kl[p], kp);
-            }
-            if (c <= 0) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo > 0) {
-            const uint4 v = shi[lo - 1];
-            const uint32_t bw[4] = {v.x, v.y, v.z, v.w};
-            int r = prefix_cmp(bw, kw[p]);
-            if (r == 0) {
-                const McFile &F = w.files[lo - 1];
-                r = bound_cmp(bw, F.hi_len, img + F.hi_at, kw[p], kl[p], kp);
-            }
-            if (r >= 0) {  // only candidates are ever tested
-                cand[p] = lo - 1;
-                rank[p] = atomicAdd(&lh[lo - 1], 1u);
-                sum256_pre(kp, kl[p], f0[p], f1[p], hh[p]);
-            }
-        }
-    }
-    {   // the workgroup's rows of the hit matrix, written once: 0 except the
-        // candidate's 1 (the test clears it when a bit is 0), 16-byte stores;
-        // the candidates through LDS (the scan's row, free until the scan)
-        uint16_t *scand = reinterpret_cast<uint16_t *>(part);
-#pragma unroll
-        for (uint32_t p = 0; p < kMcGroupPer; p++)
-            scand[p * kMcGroupThreads + t] = cand[p] == kMcNone ? (uint16_t)0xFFFFu : (uint16_t)cand[p];
-        __syncthreads();
-        const uint64_t r0 = k_begin + (uint64_t)blockIdx.x * kMcGroupProbes;
-        const uint64_t r1 = r0 + kMcGroupProbes < nkeys ? r0 + kMcGroupProbes : nkeys;
-        uint8_t *z = hit + r0 * nfile;
-        const uint32_t nz = (uint32_t)((r1 - r0) * nfile);  // <= 2,048 rows x 2,048 files
-        const uint32_t mis = (uint32_t)((uintptr_t)z & 15);
-        const uint32_t head = ((16 - mis) & 15) < nz ? ((16 - mis) & 15) : nz;
-        const uint32_t n16 = (nz - head) / 16, tail = head + 16 * n16;
-        auto one_at = [&](uint32_t o) -> uint32_t {  // byte o of the rows: the candidate's 1
-            const uint32_t row = o / nfile;
-            const uint32_t c = scand[row];
-            return c != 0xFFFFu && row * nfile + c == o ? 1u : 0u;
-        };
-        if (t < head) z[t] = (uint8_t)one_at(t);
-        u32x4 *z16 = reinterpret_cast<u32x4 *>(z + head);
-        for (uint32_t x = t; x < n16; x += kMcGroupThreads) {
-            const uint32_t o = head + 16 * x;
-            uint32_t wd[4] = {0, 0, 0, 0};
-            for (uint32_t row = o / nfile; row * nfile < o + 16; row++) {
-                const uint32_t c = scand[row];
-                const uint32_t at = row * nfile + c;
-                if (c != 0xFFFFu && at >= o && at < o + 16) wd[(at - o) >> 2] |= 1u << (8 * ((at - o) & 3));
-            }
-            z16[x] = u32x4{wd[0], wd[1], wd[2], wd[3]};
-        }
-        if (tail + t < nz) z[tail + t] = (uint8_t)one_at(tail + t);
-    }
-    __syncthreads();
-    // the workgroup's candidates grouped by file into its slots, as the level
-    // search's classify does: exclusive scan of the per-file counts (<= 2,048
-    // files, 2 per thread), the file-major grid, then the ids and records
-    const uint32_t c0 = 2 * t < nfile ? lh[2 * t] : 0u, c1 = 2 * t + 1 < nfile ? lh[2 * t + 1] : 0u;
-    part[t] = c0 + c1;
-    __syncthreads();
-    for (uint32_t d = 1; d < kMcGroupThreads; d <<= 1) {
-        const uint32_t x = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    const uint32_t ex = part[t] - c0 - c1;
-    __syncthreads();  // every lh read before it is overwritten with offsets
-    if (2 * t < nfile) {
-        lh[2 * t] = ex;
-        w.lv.grid[(uint64_t)(2 * t) * nwg + blockIdx.x] = ex;
-        w.lv.cnt[(uint64_t)(2 * t) * nwg + blockIdx.x] = c0;
-    }
-    if (2 * t + 1 < nfile) {
-        lh[2 * t + 1] = ex + c0;
-        w.lv.grid[(uint64_t)(2 * t + 1) * nwg + blockIdx.x] = ex + c0;
-        w.lv.cnt[(uint64_t)(2 * t + 1) * nwg + blockIdx.x] = c1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t p = 0; p < kMcGroupPer; p++) {
-        if (cand[p] == kMcNone) continue;
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kMcGroupProbes + p * kMcGroupThreads + t;
-        const uint64_t slot = (uint64_t)blockIdx.x * kMcGroupProbes + lh[cand[p]] + rank[p];
-        w.lv.ids[slot] = (uint32_t)(i - k_begin);
-        const McFile &F = w.files[cand[p]];
-        if (lv_compact(F)) {  // 16 bytes, and no modulo in the test
-            store_hash_rec(hh[p], (uint32_t)F.m, (uint32_t)F.mr, (uint32_t)(F.mr >> 32),
-                           reinterpret_cast<uint32_t *>(w.lv.rec + slot));
-        } else {
-            *(gptr_t<u64x2>)gbl(w.lv.rec + slot) = u64x2{hh[p][0], hh[p][1]};
-            *(gptr_t<u64x2>)gbl(w.lv.ext + slot) = u64x2{hh[p][2], hh[p][3]};
-        }
-    }
-}
-
-// Filter.Test (bloom.go:371-379) of one probe against F, the bytes below
-// in_lds from LDS (lb), the rest from the image through L2.  Sixteen
-// locations at a time, every read of a round issued before any is waited for:
-// the LDS read at a clamped address, the tail read under a predicate into its
-// own register (a read per branch whose join waits for it is sixteen
-// serialized round trips).  Lds = false: no LDS copy, every bit from src.
-template <bool Lds = true>
-__device__ __forceinline__ uint32_t filter_test(const McFile &F, const uint64_t h[4], const uint8_t *lb,
-                                                uint64_t in_lds, const uint8_t *src) {
-    // k == 0: true; m == 0 < k: Go panics, answered false
-    uint32_t r = F.k == 0 || F.m != 0;
-    const bool small = F.m <= (1ull << 30);
-    const uint32_t m32 = (uint32_t)F.m, rl = (uint32_t)F.mr, rh = (uint32_t)(F.mr >> 32);
-    for (uint32_t j0 = 0; j0 < F.k && r; j0 += 16) {
-        uint64_t p[16];
-        uint32_t lv[16], gv[16];
-#pragma unroll
-        for (uint32_t u = 0; u < 16; u++) {
-            const uint64_t x = location(h[0], h[1], h[2], h[3], j0 + u);
-            p[u] = small ? mod_small(x, m32, rl, rh) : mod_barrett(x, F.m, F.mr);
-            const uint64_t q = 8 * (p[u] >> 6) + 7 - ((p[u] & 63) >> 3);
-            const bool inl = Lds && q < in_lds;
-            lv[u] = Lds ? lb[inl ? q : 0] : 0u;
-            gv[u] = 0xFFu;
-            if (j0 + u < F.k && !inl && p[u] < F.nbits) gv[u] = gbl(src)[q];
-        }
-        uint32_t bits = 1;
-#pragma unroll
-        for (uint32_t u = 0; u < 16; u++) {
-            const uint64_t q = 8 * (p[u] >> 6) + 7 - ((p[u] & 63) >> 3);
-            const uint32_t byte = Lds && q < in_lds ? lv[u] : gv[u];
-            // bitset.Test is false past its length
-            const uint32_t bit = p[u] < F.nbits ? (byte >> (p[u] & 7)) & 1u : 0u;
-            bits &= j0 + u < F.k ? bit : 1u;
-        }
-        r = bits;
-    }
-    return r;
-}
-
-// filter_test from a probe's hash record (lv_compact tables): the k <= 16
-// locations by additions (unpack_hash_rec), the bits read as filter_test does
-// (all reads in flight, then combined).
-__device__ __forceinline__ uint32_t filter_test_rec(const McFile &F, const HashRecSteps &H0,
-                                                    uint32_t m, const uint8_t *lb, uint64_t in_lds,
-                                                    const uint8_t *src) {
-    uint32_t r[4] = {H0.r[0], H0.r[1], H0.r[2], H0.r[3]};
-    uint32_t pos[kSplitMaxK];
-#pragma unroll
-    for (uint32_t j = 0; j < kSplitMaxK; j++) {
-        const uint32_t c = j & 3, n = j >> 2;
-        pos[j] = r[c];
-        if (n < 3) {
-            const uint32_t t = r[c] + H0.st[c][n];
-            r[c] = min(t, t - m);
-        }
-    }
-    uint32_t lv[kSplitMaxK], gv[kSplitMaxK];
-#pragma unroll
-    for (uint32_t j = 0; j < kSplitMaxK; j++) {
-        const uint32_t p = pos[j];
-        const uint32_t q = 8 * (p >> 6) + 7 - ((p & 63) >> 3);
-        const bool inl = q < in_lds;
-        lv[j] = lb[inl ? q : 0u];
-        gv[j] = 0xFFu;
-        if (j < F.k && !inl && p < F.nbits) gv[j] = gbl(src)[q];
-    }
-    uint32_t bits = 1;
-#pragma unroll
-    for (uint32_t j = 0; j < kSplitMaxK; j++) {
-        const uint32_t p = pos[j];
-        const uint32_t q = 8 * (p >> 6) + 7 - ((p & 63) >> 3);
-        const uint32_t byte = q < in_lds ? lv[j] : gv[j];
-        // bitset.Test is false past its length
-        const uint32_t bit = p < F.nbits ? (byte >> (p & 7)) & 1u : 0u;
-        bits &= j < F.k ? bit : 1u;
-    }
-    return bits;
-}
-
-McWs mc_ws_layout(uint8_t *base, uint32_t nfile, uint64_t nkeys, size_t *total) {
-    McWs w{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + at : nullptr;
-        at += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
-    w.flag = reinterpret_cast<uint32_t *>(take(16));
-    w.files = reinterpret_cast<McFile *>(take(sizeof(McFile) * (size_t)(nfile ? nfile : 1)));
-    size_t lt = 0;
-    w.lv = lv_ws_layout(base ? base + at : nullptr, nfile, nkeys, &lt);
-    at += lt;
-    w.lv.files = w.files;
-    if (total) *total = at;
-    return w;
-}
-
-// ---- batched level search: Manager.searchFromLevelWithSparseIndex ---------
-//
-// For a level >= 1 (sstable/manager.go:178-207): sort.Search over the
-// level's tables in sparse-index order (sorted by MinKey, :290-303) for the
-// first whose MinKey > key, index-- when > 0, then searchFromTable's
-// SSTable.MayContain (:209-212, sstable.go:300-305) of that one table.  Per
-// probe the answer is 5 bytes (candidate table, may bit) instead of a row of
-// the nkeys x nfile matrix lsm_may_contain writes.
-//
-//  lv_classify_kernel: each workgroup takes 2,048 probes: Go's sort.Search
-//    (h = (i + j) >> 1) over the tables' 16-byte MinKey prefixes in LDS (the
-//    full keys only on a prefix tie), the candidate stored coalesced; a probe
-//    the range check rejects gets its 0 here; the others are hashed once
-//    (sum256) and counting-sorted by table in LDS into the workgroup's slots,
-//    and the workgroup's (start, count) per table goes to a table-major grid.
-//  lv_test_kernel: one workgroup per table: its row of the grid (scanned in
-//    LDS) locates its probes in every classify workgroup's slots, the
-//    filter's first 144 KiB are staged in LDS (the tail read through L2) and
-//    each probe's k bits tested there.
-// Tables beyond kLvMaxFiles take lv_probe_kernel (search over the table
-// list in global memory, bits read from the image).
-
-// The search view of table f: MinKey / MaxKey prefixes whenever the header
-// decoded (stage != 1); a table whose header did not decode searches as the
-// zero Header (MinKey "", what the oracle restates).  ok: header and filter
-// decoded (MayContain is answered only then).
-__device__ __forceinline__ McFile lv_file(const uint8_t *img, const uint64_t *file_off,
-                                          const lsm_sst_meta &M, uint32_t f) {
-    McFile F = mc_file(img, file_off, M, f);
-    if (M.stage == 2) {  // header decoded, filter not: search by its MinKey
-        const uint8_t *base = img + file_off[f];
-        key_prefix(base + M.min_key_off, M.min_key_len, F.lo);
-        key_prefix(base + M.max_key_off, M.max_key_len, F.hi);
-    } else if (M.stage == 1) {
-        F.lo_len = F.hi_len = 0;
-    }
-    return F;
-}
-
-__global__ __launch_bounds__(256) void lv_prep_kernel(const uint8_t *img, const uint64_t *file_off,
-                                                      const lsm_sst_meta *meta, uint32_t nfile,
-                                                      LvWs w) {
-    const uint32_t f = blockIdx.x * 256 + threadIdx.x;
-    if (f < nfile) w.files[f] = lv_file(img, file_off, meta[f], f);
-}
-
-// sort.Search(n, MinKey_h > key) exactly as Go's sort.go runs it.
-template <typename LoAt>
-__device__ __forceinline__ uint32_t lv_search(uint32_t nfile, LoAt lo_prefix, const McFile *files,
-                                              const uint8_t *img, const uint32_t kw[4], uint64_t kl,
-                                              const uint8_t *kp) {
-    uint32_t i = 0, j = nfile;
-    while (i < j) {
-        const uint32_t h = (uint32_t)(((uint64_t)i + j) >> 1);
-        uint32_t bw[4];
-        lo_prefix(h, bw);
-        int c = prefix_cmp(bw, kw);
-        if (c == 0) {
-            const McFile &F = files[h];
-            c = bound_cmp(bw, F.lo_len, img + F.lo_at, kw, kl, kp);
-        }
-        if (c <= 0) i = h + 1;  // !f(h)
-        else j = h;
-    }
-    return i;
-}
-
-__global__ __launch_bounds__(kLvThreads) void lv_classify_kernel(const uint8_t *img, uint32_t nfile,
-                                                                 const uint8_t *keys, const uint64_t *koff,
-                                                                 uint64_t k_begin, uint64_t nkeys, LvWs w,
-                                                                 uint32_t nwg, int32_t *table,
-                                                                 uint8_t *may) {
-    __shared__ uint4 slo[kLvMaxFiles];
-    __shared__ uint32_t lh[kLvMaxFiles];
-    __shared__ uint32_t part[kLvThreads];
-    const uint32_t t = threadIdx.x;
-    for (uint32_t f = t; f < nfile; f += kLvThreads) {
-        const McFile &F = w.files[f];
-        slo[f] = make_uint4(F.lo[0], F.lo[1], F.lo[2], F.lo[3]);
-        lh[f] = 0;
-    }
-    uint64_t k0[kLvPer], kl[kLvPer], f0[kLvPer], f1[kLvPer];
-#pragma unroll
-    for (uint32_t p = 0; p < kLvPer; p++) {
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kLvProbes + p * kLvThreads + t;
-        k0[p] = i < nkeys ? koff[i] : 0;
-        kl[p] = i < nkeys ? koff[i + 1] - k0[p] : 0;
-    }
-#pragma unroll
-    for (uint32_t p = 0; p < kLvPer; p++) {
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kLvProbes + p * kLvThreads + t;
-        f0[p] = i < nkeys ? ldg_u64_unaligned(keys + k0[p]) : 0;
-        f1[p] = i < nkeys ? ldg_u64_unaligned(keys + k0[p] + 8) : 0;
-    }
-    uint32_t kw[kLvPer][4];
-#pragma unroll
-    for (uint32_t p = 0; p < kLvPer; p++) {
-        const uint64_t l = kl[p];
-        if (l < 8) { f0[p] &= l ? (~0ull >> (64 - 8 * l)) : 0; f1[p] = 0; }
-        else if (l < 16) f1[p] &= l > 8 ? (~0ull >> (128 - 8 * l)) : 0;
-        kw[p][0] = __builtin_bswap32((uint32_t)f0[p]);
-        kw[p][1] = __builtin_bswap32((uint32_t)(f0[p] >> 32));
-        kw[p][2] = __builtin_bswap32((uint32_t)f1[p]);
-        kw[p][3] = __builtin_bswap32((uint32_t)(f1[p] >> 32));
-    }
-    __syncthreads();
-    auto lo_lds = [&](uint32_t h, uint32_t bw[4]) {
-        const uint4 v = slo[h];
-        bw[0] = v.x; bw[1] = v.y; bw[2] = v.z; bw[3] = v.w;
-    };
-    uint32_t cand[kLvPer], rank[kLvPer];
-    uint64_t hh[kLvPer][4];
-#pragma unroll
-    for (uint32_t p = 0; p < kLvPer; p++) {
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kLvProbes + p * kLvThreads + t;
-        cand[p] = kMcNone;
-        if (i >= nkeys) continue;
-        const uint8_t *kp = keys + k0[p];
-        const uint32_t lo = lv_search(nfile, lo_lds, w.files, img, kw[p], kl[p], kp);
-        const uint32_t idx = lo ? lo - 1 : 0;  // manager.go:189-191
-        table[i] = (int32_t)idx;
-        // MayContain (sstable.go:301): lo > 0 means f(lo - 1) was evaluated
-        // false, i.e. MinKey <= key; then MaxKey >= key and a decoded filter
-        bool test = false;
-        if (lo > 0) {
-            const McFile &F = w.files[idx];
-            if (F.ok) {
-                int r = prefix_cmp(F.hi, kw[p]);
-                if (r == 0) r = bound_cmp(F.hi, F.hi_len, img + F.hi_at, kw[p], kl[p], kp);
-                test = r >= 0;
-            }
-        }
-        may[i] = test ? 1 : 0;  // the test clears a candidate whose bit is 0
-        if (!test) continue;
-        cand[p] = idx;
-        rank[p] = atomicAdd(&lh[idx], 1u);
-        sum256_pre(kp, kl[p], f0[p], f1[p], hh[p]);
-    }
-    __syncthreads();
-    // exclusive scan of the per-table counts (<= 2,048 tables, 2 per thread)
-    const uint32_t c0 = 2 * t < nfile ? lh[2 * t] : 0u, c1 = 2 * t + 1 < nfile ? lh[2 * t + 1] : 0u;
-    part[t] = c0 + c1;
-    __syncthreads();
-    for (uint32_t d = 1; d < kLvThreads; d <<= 1) {
-        const uint32_t x = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    const uint32_t ex = part[t] - c0 - c1;
-    __syncthreads();  // every lh read before it is overwritten with offsets
-    if (2 * t < nfile) {
-        lh[2 * t] = ex;
-        w.grid[(uint64_t)(2 * t) * nwg + blockIdx.x] = ex;
-        w.cnt[(uint64_t)(2 * t) * nwg + blockIdx.x] = c0;
-    }
-    if (2 * t + 1 < nfile) {
-        lh[2 * t + 1] = ex + c0;
-        w.grid[(uint64_t)(2 * t + 1) * nwg + blockIdx.x] = ex + c0;
-        w.cnt[(uint64_t)(2 * t + 1) * nwg + blockIdx.x] = c1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t p = 0; p < kLvPer; p++) {
-        if (cand[p] == kMcNone) continue;
-        const uint64_t i = k_begin + (uint64_t)blockIdx.x * kLvProbes + p * kLvThreads + t;
-        const uint64_t slot = (uint64_t)blockIdx.x * kLvProbes + lh[cand[p]] + rank[p];
-        w.ids[slot] = (uint32_t)(i - k_begin);
-        const McFile &F = w.files[cand[p]];
-        if (lv_compact(F)) {
-            store_hash_rec(hh[p], (uint32_t)F.m, (uint32_t)F.mr, (uint32_t)(F.mr >> 32),
-                           reinterpret_cast<uint32_t *>(w.rec + slot));
-        } else {
-            *(gptr_t<u64x2>)gbl(w.rec + slot) = u64x2{hh[p][0], hh[p][1]};
-            *(gptr_t<u64x2>)gbl(w.ext + slot) = u64x2{hh[p][2], hh[p][3]};
-        }
-    }
-}
-
-// The filter words of F: the first `cap` bytes into LDS from the 16-byte
-// boundary below them (aligned 16-byte global->LDS loads, all in flight, the
-// wave chunks rotated per file so the fills of files at equal offsets
-// spread over the channels).  -> bytes staged.
-__device__ __forceinline__ uint64_t stage_filter(const uint8_t *src, uint64_t nbits, uint8_t *lds,
-                                                 uint32_t cap, uint32_t rot_seed, uint32_t &delta) {
-    const uint64_t nb = 8 * (nbits / 64 + ((nbits & 63) != 0));
-    delta = (uint32_t)((uintptr_t)src & 15);
-    const uint64_t in_lds = nb < cap - 16 ? nb : cap - 16;
-    const uint4 *src16 = reinterpret_cast<const uint4 *>(src - delta);
-    const uint32_t n16 = (uint32_t)((delta + in_lds + 15) / 16);
-    const uint32_t nwc = (n16 + kWave - 1) / kWave, wave = threadIdx.x / kWave;
-    const uint32_t rot = nwc ? (rot_seed * 37u) % nwc : 0;
-    const uint32_t nwaves = blockDim.x / kWave;
-    for (uint32_t cl = wave; cl < nwc; cl += nwaves) {
-        const uint32_t c = cl + rot < nwc ? cl + rot : cl + rot - nwc;
-        const uint32_t xw = c * kWave, x = xw + (threadIdx.x & (kWave - 1));
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void *)(src16 + (x < n16 ? x : n16 - 1)),
-            (__attribute__((address_space(3))) void *)(lds + 16 * xw), 16, 0, 0);
-    }
-    return n16 ? in_lds : 0;
-}
-
-
-// Matrix = false: the level search's may-bit per probe (may[k]); true: the
-// all-tables form's hit matrix (may[k * nfile + f]), run only when the grouped
-// path holds (*flag).  Either way classify wrote each candidate's 1 and the
-// test clears the candidates whose bit is 0.
-template <bool Matrix>
-__global__ __launch_bounds__(kLvThreads) void lv_test_kernel(const uint8_t *img, uint32_t nfile,
-                                                             uint32_t nwg, LvWs w, uint64_t k_begin,
-                                                             uint8_t *may, const uint32_t *flag) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t fbytes[];
-    __shared__ uint32_t sb[kLvMaxWgs + 1];  // first probe of each workgroup's segment
-    __shared__ uint32_t sg[kLvMaxWgs];      // its first slot in that workgroup
-    __shared__ uint32_t part[kLvThreads];
-    if (Matrix && !flag[0]) return;
-    const uint32_t f = blockIdx.x, t = threadIdx.x;
-    // the table's segments: counts scanned (nwg <= 1,024: one per thread)
-    const uint32_t c = t < nwg ? w.cnt[(uint64_t)f * nwg + t] : 0u;
-    if (t < nwg) sg[t] = w.grid[(uint64_t)f * nwg + t];
-    part[t] = c;
-    __syncthreads();
-    for (uint32_t d = 1; d < kLvThreads; d <<= 1) {
-        const uint32_t x = t >= d ? part[t - d] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    if (t < nwg) sb[t] = part[t] - c;
-    if (t == 0) sb[nwg] = part[kLvThreads - 1];
-    __syncthreads();
-    const uint32_t total = sb[nwg];
-    if (total == 0) return;
-    const McFile F = w.files[f];
-    // the slot of the table's probe q: binary search of its segment
-    auto slot_of = [&](uint32_t q) -> uint64_t {
-        uint32_t a = 0, b = nwg;  // last segment with sb <= q
-        while (b - a > 1) {
-            const uint32_t mid = (a + b) >> 1;
-            if (sb[mid] <= q) a = mid;
-            else b = mid;
-        }
-        return (uint64_t)a * kLvProbes + sg[a] + (q - sb[a]);
-    };
-    const bool compact = lv_compact(F);
-    const uint32_t m32 = (uint32_t)F.m;
-    // 2^64 mod m for the record's carried steps
-    const uint32_t c64 = compact ? (mod_small(~0ull, m32, (uint32_t)F.mr, (uint32_t)(F.mr >> 32)) + 1) % m32 : 0u;
-    uint32_t q = t, id = 0;
-    u32x4 x = {0, 0, 0, 0}, y = {0, 0, 0, 0};
-    if (q < total) {  // the first probe's hash in flight during the fill
-        const uint64_t sl = slot_of(q);
-        id = w.ids[sl];
-        x = w.rec[sl];
-        if (!compact) y = w.ext[sl];
-    }
-    const uint8_t *src = img + F.words_at;
-    uint32_t delta;
-    const uint64_t in_lds = stage_filter(src, F.nbits, fbytes, kMcLdsBytes, f, delta);
-    __asm__ __volatile__("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const uint8_t *lb = fbytes + delta;
-    while (q < total) {
-        const uint32_t qn = q + kLvThreads;
-        uint32_t idn = 0;
-        u32x4 xn = {0, 0, 0, 0}, yn = {0, 0, 0, 0};
-        if (qn < total) {
-            const uint64_t sl = slot_of(qn);
-            idn = w.ids[sl];
-            xn = w.rec[sl];
-            if (!compact) yn = w.ext[sl];
-        }
-        uint32_t r;
-        if (compact) {
-            r = filter_test_rec(F, unpack_hash_rec(x, m32, c64), m32, lb, in_lds, src);
-        } else {
-            const uint64_t h[4] = {(uint64_t)x.y << 32 | x.x, (uint64_t)x.w << 32 | x.z,
-                                   (uint64_t)y.y << 32 | y.x, (uint64_t)y.w << 32 | y.z};
-            r = filter_test(F, h, lb, in_lds, src);
-        }
-        if (Matrix) {
-            if (!r) may[(k_begin + id) * nfile + f] = 0;  // classify wrote the 1
-        }
-        else if (!r) may[k_begin + id] = 0;
-        q = qn;
-        id = idn;
-        x = xn;
-        y = yn;
-    }
-}
-
-// More tables than the LDS search holds: per probe, the search over the
-// table list in global memory and the bits read from the image.
-__global__ __launch_bounds__(256) void lv_probe_kernel(const uint8_t *img, uint32_t nfile,
-                                                       const uint8_t *keys, const uint64_t *koff,
-                                                       uint64_t nkeys, LvWs w, int32_t *table,
-                                                       uint8_t *may) {
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < nkeys;
-         i += (uint64_t)gridDim.x * 256) {
-        const uint64_t k0 = koff[i], kl = koff[i + 1] - k0;
-        const uint8_t *kp = keys + k0;
-        uint32_t kw[4];
-        for (uint32_t j = 0; j < 4; j++) kw[j] = be_word_at(kp, kl, j);
-        auto lo_g = [&](uint32_t h, uint32_t bw[4]) {
-            for (int j = 0; j < 4; j++) bw[j] = w.files[h].lo[j];
-        };
-        const uint32_t lo = lv_search(nfile, lo_g, w.files, img, kw, kl, kp);
-        const uint32_t idx = lo ? lo - 1 : 0;
-        table[i] = (int32_t)idx;
-        uint8_t r = 0;
-        if (lo > 0 && w.files[idx].ok) {
-            const McFile &F = w.files[idx];
-            if (bound_cmp_fast(F.hi, F.hi_len, img + F.hi_at, kw, kl, kp) >= 0) {
-                uint64_t h[4];
-                sum256(kp, kl, h);
-                const uint8_t *src = img + F.words_at;
-                r = (uint8_t)filter_test<false>(F, h, nullptr, 0, src);
-            }
-        }
-        may[i] = r;
-    }
-}
-
-// ---- batched Get past MayContain: Iterator.Seek + GetValueByOffset ---------
-//
-// searchFromTable (sstable/manager.go:209-223) after its MayContain: Seek
-// (sstable/block/index.go:157-181: left, right := 0, n; mid := left +
-// (right-left)/2; Indexes[mid].Key < target -> left = mid + 1, else right =
-// mid; valid only if Indexes[left].Key == target) over the table's decoded
-// IndexBlock, then Iterator.Value -> GetValueByOffset (sstable.go:271-296:
-// Seek to the entry's offset, Value.DecodeFrom, kv.go:181-200).  One thread
-// per probe; the bisection compares 16-byte big-endian prefixes loaded from
-// the index entries in the image (the bytes past them only on a prefix tie).
-struct GetArgs {
-    const uint8_t *img;
-    const uint64_t *file_off, *file_len;
-    const lsm_sst_meta *meta;
-    uint32_t nfile;
-    const uint64_t *rec_base;
-    const lsm_rec_desc *idx_desc;
-    const int64_t *idx_value;
-    const uint8_t *keys;
-    const uint64_t *koff;
-    uint64_t nkeys;
-    const int32_t *table;
-    const uint8_t *may;
-    int32_t *result;
-    lsm_rec_desc *value;
-    const uint8_t *tree;  // the Seek tree (lsm_level_get_tree_build), or null
-    uint32_t tree_nidx;   // the tree's max_nidx: larger tables walk the index
-    uint32_t tree_top;    // levels in the tree's top block (1-3)
-    uint64_t tree_stride; // bytes per table
-};
-
-// The Seek tree.  Go's bisection over a table's n index entries visits a
-// fixed binary tree of midpoints (the midpoint of [l, r) is l + (r - l)/2
-// whatever the keys hold), so it is laid down once per level -- as the
-// decoded IndexBlocks are, when the level is loaded -- in 128-byte blocks of
-// three tree levels: seven nodes of the key's 16-byte big-endian prefix
-// (bytes 0-111) and its length capped at 0xFFFF (u16 at 112 + 2j).  A probe
-// then reads one 128-byte line per three steps instead of an index
-// descriptor and a key line per step, and takes exactly Go's steps, so any
-// index -- sorted or not -- lands where Seek lands.  Blocks: with D =
-// bitlen(max_nidx) levels, the top block holds the first t = D - 3(G - 1)
-// levels (G = ceil(D / 3) groups); group g >= 1 holds 2^t 8^(g-1) blocks,
-// block i's child c (the three steps taken in it, first step in the high
-// bit) being block 8i + c of the next group (the top block's children: its
-// exit c < 2^t).  Node j of a block (0-6, breadth-first) lies on the path
-// (block path, bits of j + 1 below the leading one; 1 = the right half).
-struct TreeShape {
-    uint32_t D, G, t;
-    uint64_t blocks;
-};
-
-__host__ __device__ inline TreeShape tree_shape(uint32_t max_nidx) {
-    TreeShape T{0, 0, 0, 0};
-    while (T.D < 32 && (max_nidx >> T.D)) T.D++;
-    if (T.D == 0) return T;
-    T.G = (T.D + 2) / 3;
-    T.t = T.D - 3 * (T.G - 1);
-    T.blocks = 1 + ((1ull << T.t) * (((1ull << (3 * (T.G - 1))) - 1) / 7));
-    return T;
-}
-
-
-// One thread per (table, block, node slot 0-7; slot 7 idle).
-__global__ __launch_bounds__(256) void get_tree_build_kernel(GetArgs a, uint8_t *tree, TreeShape T) {
-    const uint64_t gid = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint64_t f = gid / (8 * T.blocks);
-    if (f >= a.nfile) return;
-    const uint64_t b = (gid - f * 8 * T.blocks) >> 3;
-    const uint32_t j = (uint32_t)(gid & 7);
-    const uint32_t n = a.meta[f].nidx;
-    if (j == 7 || n > a.tree_nidx) return;
-    // the block's group g and index i in it, its root's depth and path
-    uint64_t off = 1, cnt = 1ull << T.t, i = 0;
-    uint32_t depth = 0;
-    if (b > 0) {
-        depth = T.t;
-        while (b >= off + cnt) {
-            off += cnt;
-            cnt *= 8;
-            depth += 3;
-        }
-        i = b - off;
-    }
-    const uint32_t levels = b == 0 ? T.t : 3;
-    const uint32_t ld = 31 - __builtin_clz(j + 1);
-    if (ld >= levels) return;
-    const uint64_t path = (i << ld) | (uint64_t)(j + 1 - (1u << ld));
-    depth += ld;
-    uint32_t l = 0, r = n;
-    for (uint32_t s = depth; s-- > 0 && l < r;) {
-        const uint32_t mid = l + (r - l) / 2;
-        if ((path >> s) & 1) l = mid + 1;
-        else r = mid;
-    }
-    uint32_t kw[4] = {0, 0, 0, 0}, len = 0;  // an empty interval is never walked
-    if (l < r) {
-        const uint64_t base = a.rec_base ? a.rec_base[f] : a.file_off[f] / 4;
-        const lsm_rec_desc d = a.idx_desc[base + l + (r - l) / 2];
-        key_prefix(a.img + d.rec_off + 4, d.key_len, kw);
-        len = d.key_len < 0xFFFFu ? d.key_len : 0xFFFFu;
-    }
-    uint8_t *blk = tree + f * a.tree_stride + b * 128;
-    u32x4 o;
-    o.x = kw[0]; o.y = kw[1]; o.z = kw[2]; o.w = kw[3];
-    *reinterpret_cast<u32x4 *>(blk + 16 * j) = o;
-    *reinterpret_cast<uint16_t *>(blk + 112 + 2 * j) = (uint16_t)len;
-}
-
-// Go's comparison of index entry (prefix ew, length el -- exact up to 16,
-// capped past it -- at mid) against the probe: the prefix, then the lengths
-// when either key fits in 16 bytes (the bytes both hold are then all in the
-// prefixes), the bytes past 16 otherwise.
-__device__ __forceinline__ int tree_cmp(const GetArgs &a, uint64_t base, uint32_t mid, const uint32_t ew[4],
-                                        uint32_t el, const uint32_t kw[4], uint64_t kl, const uint8_t *kp) {
-    int c = prefix_cmp(ew, kw);
-    if (c == 0) {
-        if (el <= 16 || kl <= 16) {
-            c = (uint64_t)el < kl ? -1 : (uint64_t)el > kl ? 1 : 0;
-        } else {
-            const lsm_rec_desc d = a.idx_desc[base + mid];
-            c = bound_cmp(ew, d.key_len, a.img + d.rec_off + 4, kw, kl, kp);
-        }
-    }
-    return c;
-}
-
-// searchFromTable past MayContain (manager.go:209-223) on table t: Go's
-// bisection (through the Seek tree, or over the index), the exact-match
-// test, then GetValueByOffset (sstable.go:271-296).  -> a lsm_get_result;
-// the value's view in v on LSM_GET_FOUND.
-__device__ __forceinline__ int32_t get_in_table(const GetArgs &a, uint32_t t, const uint32_t kw[4],
-                                                uint64_t kl, const uint8_t *kp, lsm_rec_desc &v) {
-    int32_t res = LSM_GET_ABSENT;
-    // the table's top tree block is loaded beside its meta (its address does
-    // not depend on the index size): one dependent round trip fewer
-    u32x4 top[8];
-    const uint8_t *tb = a.tree + (uint64_t)t * a.tree_stride;
-    if (a.tree) {
-        const u32x4 *B = reinterpret_cast<const u32x4 *>(tb);
-#pragma unroll
-        for (int q = 0; q < 8; q++) top[q] = B[q];
-    }
-    const lsm_sst_meta &M = a.meta[t];
-    const uint64_t fo = a.file_off[t], fl = a.file_len[t];
-    const uint64_t base = a.rec_base ? a.rec_base[t] : fo / 4;
-    const uint32_t n = M.nidx;
-    uint32_t left = 0, right = n;
-    bool hit = false;
-    if (a.tree && n <= a.tree_nidx) {
-        // Go's bisection through the Seek tree: one 128-byte block per
-        // three steps.  The final left is the midpoint of the last step
-        // that set right, so Indexes[left].Key == target is that step's
-        // comparison being 0 (hit).
-        uint64_t off = 0, cnt = 1, bi = 0;
-        uint32_t levels = a.tree_top;
-        // the steps of one block (nodes nd), then the child block's position
-        auto walk_block = [&](const u32x4 (&nd)[8]) {
-            uint32_t j = 0;
-#pragma unroll
-            for (uint32_t d = 0; d < 3; d++) {
-                if (d >= levels || left >= right) break;
-                u32x4 e = nd[0];
-                if (d == 1) e = j == 1 ? nd[1] : nd[2];
-                if (d == 2) {
-                    const u32x4 lo = j == 3 ? nd[3] : nd[4], hi = j == 5 ? nd[5] : nd[6];
-                    e = j < 5 ? lo : hi;
-                }
-                const uint32_t lw = j < 2 ? nd[7].x : j < 4 ? nd[7].y : j < 6 ? nd[7].z : nd[7].w;
-                const uint32_t el = (lw >> (16 * (j & 1))) & 0xFFFFu;
-                const uint32_t ew[4] = {e.x, e.y, e.z, e.w};
-                const uint32_t mid = left + (right - left) / 2;
-                const int c = tree_cmp(a, base, mid, ew, el, kw, kl, kp);
-                if (c < 0) {
-                    left = mid + 1;
-                    j = 2 * j + 2;
-                } else {
-                    right = mid;
-                    hit = c == 0;
-                    j = 2 * j + 1;
-                }
-            }
-            // the child block: group g + 1, index 8 bi + the exit's rank
-            bi = off == 0 ? j - ((1u << levels) - 1) : 8 * bi + (j - 7);
-            off += cnt;
-            cnt = off == 1 ? (1ull << a.tree_top) : cnt * 8;
-            levels = 3;
-        };
-        if (left < right) walk_block(top);  // the top block, already loaded
-        while (left < right) {
-            const u32x4 *B = reinterpret_cast<const u32x4 *>(tb + (off + bi) * 128);
-            u32x4 nd[8];
-#pragma unroll
-            for (int q = 0; q < 8; q++) nd[q] = B[q];
-            walk_block(nd);
-        }
-    } else {
-        // Go's bisection over the index (a variant loading both possible
-        // next midpoints' entries before each compare measured slower:
-        // 0.549 vs 0.375 ms per 1M-key Get, 3.0 GB of HBM traffic per
-        // call -- round 5, A/B)
-        while (left < right) {
-            const uint32_t mid = left + (right - left) / 2;
-            const lsm_rec_desc d = a.idx_desc[base + mid];
-            const uint8_t *ep = a.img + d.rec_off + 4;
-            uint32_t ew[4];
-            key_prefix(ep, d.key_len, ew);
-            const int c = bound_cmp_fast(ew, d.key_len, ep, kw, kl, kp);
-            if (c < 0) left = mid + 1;  // Indexes[mid].Key < target
-            else right = mid;
-        }
-        if (left < n) {
-            const lsm_rec_desc d = a.idx_desc[base + left];
-            const uint8_t *ep = a.img + d.rec_off + 4;
-            hit = d.key_len == kl && go_cmp(ep, d.key_len, kp, kl) == 0;
-        }
-    }
-    if (hit) {
-        const int64_t off = a.idx_value[base + left];
-        if (off < 0) {
-            res = LSM_GET_SEEK_FAILED;  // file.Seek to a negative offset
-        } else {
-            // Value.DecodeFrom from the file at off: u32 length, cap, bytes
-            const uint64_t rem = (uint64_t)off < fl ? fl - (uint64_t)off : 0;
-            if (rem < 4) {
-                res = LSM_GET_VALUE_LENGTH;
-            } else {
-                const uint8_t *vp = a.img + fo + (uint64_t)off;
-                const uint32_t vl = (uint32_t)vp[0] | (uint32_t)vp[1] << 8 | (uint32_t)vp[2] << 16 |
-                                    (uint32_t)vp[3] << 24;
-                if (vl > (1u << 30)) res = LSM_GET_VALUE_TOO_LONG;
-                else if (rem - 4 < vl) res = LSM_GET_VALUE_SHORT;
-                else {
-                    res = LSM_GET_FOUND;
-                    v = lsm_rec_desc{fo + (uint64_t)off, 0, vl};
-                }
-            }
-        }
-    }
-    return res;
-}
-
-__global__ __launch_bounds__(256) void level_get_kernel(GetArgs a) {
-    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.nkeys) return;
-    int32_t res = LSM_GET_ABSENT;
-    lsm_rec_desc v{0, 0, 0};
-    const int32_t t = a.table[i];
-    if (a.may[i] && t >= 0 && (uint32_t)t < a.nfile) {
-        const uint64_t k0 = a.koff[i], kl = a.koff[i + 1] - k0;
-        const uint8_t *kp = a.keys + k0;
-        uint32_t kw[4];
-        key_prefix(kp, kl, kw);
-        res = get_in_table(a, (uint32_t)t, kw, kl, kp, v);
-    }
-    a.result[i] = res;
-    a.value[i] = v;
-}
-
-// ---- level 0: Manager.searchFromLevel0 (manager.go:160-176) ---------------
-//
-// Level 0's tables overlap (each is one memtable flush, newest first:
-// addNewSSTables prepends, manager.go:284-287), so a key is searched in every
-// table in order: searchFromTable (:209-223) -- MayContain (the range check,
-// then Filter.Test), Seek, the value -- and the first non-nil value or error
-// ends the search.  One thread per key: the key is hashed once, the tables'
-// bounds and filter shapes are staged per workgroup in LDS tiles, and a
-// false positive or a Seek miss moves on to the next table.
-constexpr uint32_t kL0Threads = 256;
-constexpr uint32_t kL0Tile = 64;
-
-// Filter.Test (bloom.go:371-379) of an image's stored filter, every m (the
-// per-probe path's form: sixteen bit reads in flight at a time).
-__device__ __forceinline__ uint32_t filter_test_any(const McFile &F, const uint64_t h[4], const uint8_t *img) {
-    const uint64_t m = F.m;
-    // hashNum 0: true; m == 0 < k: Go panics, answered false
-    uint32_t r = F.k == 0 || m != 0;
-    for (uint32_t j0 = 0; j0 < F.k && r; j0 += 16) {
-        uint32_t bits = 1;
-#pragma unroll
-        for (uint32_t u = 0; u < 16; u++) {
-            const uint32_t j = j0 + u;
-            if (j < F.k) {
-                const uint64_t x = location(h[0], h[1], h[2], h[3], j);
-                const uint64_t p = m < (1ull << 63) ? mod_barrett(x, m, F.mr) : x % m;
-                bits &= p < F.nbits ? (uint32_t)(img[F.words_at + 8 * (p >> 6) + 7 - ((p & 63) >> 3)] >> (p & 7)) & 1
-                                    : 0u;
-            }
-        }
-        r &= bits;
-    }
-    return r;
-}
-
-__global__ __launch_bounds__(kL0Threads) void level0_get_kernel(GetArgs a, int32_t *table_out) {
-    __shared__ McFile tile[kL0Tile];
-    const uint64_t i = (uint64_t)blockIdx.x * kL0Threads + threadIdx.x;
-    const bool act = i < a.nkeys;
-    uint64_t k0 = 0, kl = 0;
-    uint32_t kw[4] = {0, 0, 0, 0};
-    if (act) {
-        k0 = a.koff[i];
-        kl = a.koff[i + 1] - k0;
-        key_prefix(a.keys + k0, kl, kw);
-    }
-    const uint8_t *kp = a.keys + k0;
-    uint64_t h[4] = {0, 0, 0, 0};
-    bool hashed = false, done = !act;
-    int32_t res = LSM_GET_ABSENT, tab = -1;
-    lsm_rec_desc v{0, 0, 0};
-    for (uint32_t f0 = 0; f0 < a.nfile; f0 += kL0Tile) {
-        const uint32_t nt = a.nfile - f0 < kL0Tile ? a.nfile - f0 : kL0Tile;
-        __syncthreads();  // the previous tile is consumed
-        for (uint32_t t = threadIdx.x; t < nt; t += kL0Threads) tile[t] = mc_file(a.img, a.file_off, a.meta[f0 + t], f0 + t);
-        __syncthreads();
-        for (uint32_t t = 0; t < nt && !done; t++) {
-            const McFile &F = tile[t];
-            // MayContain (sstable.go:300-305): a table whose header or filter
-            // did not decode answers false (the Manager never loads one)
-            if (!F.ok) continue;
-            if (bound_cmp_fast(F.lo, F.lo_len, a.img + F.lo_at, kw, kl, kp) > 0 ||
-                bound_cmp_fast(F.hi, F.hi_len, a.img + F.hi_at, kw, kl, kp) < 0)
-                continue;
-            if (!hashed) {
-                sum256(kp, kl, h);
-                hashed = true;
-            }
-            if (!filter_test_any(F, h, a.img)) continue;
-            const int32_t r = get_in_table(a, f0 + t, kw, kl, kp, v);
-            if (r != LSM_GET_ABSENT) {  // a value or an error: the search ends
-                res = r;
-                tab = (int32_t)(f0 + t);
-                done = true;
-            }
-        }
-    }
-    if (act) {
-        a.result[i] = res;
-        a.value[i] = v;
-        table_out[i] = tab;
-    }
-}
-
-// ---- the whole tree: Manager.Search (manager.go:99-133) --------------------
-//
-// Level 0 as searchFromLevel0 (:160-176), then each non-empty level 1..6 as
-// searchFromLevelWithSparseIndex + searchFromTable (:178-223); the first value
-// or error ends a key's search.  The tree is one table list, level L being
-// tables [start[L], start[L + 1]); files = lsm_level_index_build over it.
-// One thread per key does the whole of Search: the key is hashed once (at its
-// first table whose range admits it), a deeper level is searched only while
-// the key is still unanswered, and the filter bits are read from the image.
-// (The tables' MinKey prefixes staged in LDS for the sort.Search steps gave
-// 0.508 against 0.518 ms per 1M keys on the bench tree: not kept.)
-// A grouped form (every level's candidates classified and hashed once, one
-// filter test per table from LDS as lv_test_kernel, then the Gets in Manager
-// order) measured slower on the bench tree, 1.21 against 0.52 ms per 1M keys
-// (DESIGN.md sections 5 and 7): its passes are short latency-bound launches and the
-// test's one workgroup per table follows the tree's skew.
-constexpr uint32_t kSrLevels = LSM_SEARCH_LEVELS;
-constexpr uint32_t kSrMaxGrid = 8192;  // workgroups (grid-stride past them)
-
-struct SrShape {
-    uint32_t start[kSrLevels + 1];
-};
-
-// lsm_db_get's instantiation (DB): database.Get's second half.  A key the
-// memtables answered (db.mem_result, lsm_memtable_search's) does none of the
-// search -- no hash, no filter test, no Seek -- and keeps the value view the
-// memtable search wrote; the others run Search as below and db.src says where
-// Get's value lies.  lsm_search's kernel (search_body<false>) compiles none of
-// this and takes the arguments it always took.
-struct SrDb {
-    const int32_t *mem_result;
-    int32_t *src;
-    int mode;
-};
-
-template <bool DB>
-__device__ __forceinline__ void search_body(const GetArgs &a, const McFile *files, const SrShape &S,
-                                            int32_t *level_out, int32_t *table_out, const SrDb &db) {
-    const uint32_t n0 = S.start[1];
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < a.nkeys;
-         i += (uint64_t)gridDim.x * 256) {
-        if constexpr (DB) {
-            // database.go:29: `if value != nil` -- EXACT sends a tombstone's nil on to the tables
-            const int32_t m = db.mem_result[i];
-            if (m == LSM_MEM_VALUE || (m == LSM_MEM_DELETED && db.mode == LSM_DBGET_TOMBSTONE_HIDES)) {
-                a.result[i] = LSM_GET_ABSENT;
-                table_out[i] = -1;
-                level_out[i] = -1;
-                db.src[i] = LSM_SRC_MEMTABLE;
-                continue;
-            }
-        }
-        const uint64_t k0 = a.koff[i], kl = a.koff[i + 1] - k0;
-        const uint8_t *kp = a.keys + k0;
-        uint32_t kw[4];
-        key_prefix(kp, kl, kw);
-        uint64_t h[4] = {0, 0, 0, 0};
-        bool hashed = false;
-        int32_t res = LSM_GET_ABSENT, tab = -1, lev = -1;
-        lsm_rec_desc v{0, 0, 0};
-        // step s: level-0 table s, then level s - n0 + 1
-        for (uint32_t s = 0; s < n0 + kSrLevels - 1 && res == LSM_GET_ABSENT; s++) {
-            const uint32_t L = s < n0 ? 0 : s - n0 + 1;
-            uint32_t f = s;
-            bool in_range;
-            if (L == 0) {  // searchFromLevel0: every table, MayContain's range check
-                const McFile &F = files[f];
-                in_range = F.ok && bound_cmp_fast(F.lo, F.lo_len, a.img + F.lo_at, kw, kl, kp) <= 0 &&
-                           bound_cmp_fast(F.hi, F.hi_len, a.img + F.hi_at, kw, kl, kp) >= 0;
-            } else {  // searchFromLevelWithSparseIndex over the level's sub-range
-                const uint32_t base = S.start[L], n = S.start[L + 1] - base;
-                if (n == 0) continue;  // manager.go:194: no candidate in an empty level
-                auto lo_at = [&](uint32_t x, uint32_t bw[4]) {
-                    for (int j = 0; j < 4; j++) bw[j] = files[base + x].lo[j];
-                };
-                const uint32_t lo = lv_search(n, lo_at, files + base, a.img, kw, kl, kp);
-                f = base + (lo ? lo - 1 : 0);  // manager.go:189-191
-                const McFile &F = files[f];
-                // MayContain: lo > 0 means MinKey <= key; then MaxKey >= key
-                in_range = lo > 0 && F.ok && bound_cmp_fast(F.hi, F.hi_len, a.img + F.hi_at, kw, kl, kp) >= 0;
-            }
-            if (!in_range) continue;
-            if (!hashed) {
-                sum256(kp, kl, h);
-                hashed = true;
-            }
-            const McFile &F = files[f];
-            // Filter.Test as each level's own entry runs it (they differ only
-            // on a corrupted m >= 2^63): lsm_level0_get's, lv_probe_kernel's.
-            // All k bits in flight: reading the first two bits first (they
-            // reject most absent keys of a 15 % full filter) measured slower,
-            // 0.588 against 0.518 ms per 1M keys
-            const uint32_t pass = L == 0 ? filter_test_any(F, h, a.img)
-                                         : filter_test<false>(F, h, nullptr, 0, a.img + F.words_at);
-            if (!pass) continue;
-            res = get_in_table(a, f, kw, kl, kp, v);
-            if (res != LSM_GET_ABSENT) {  // a value or an error: the search ends
-                tab = (int32_t)f;
-                lev = (int32_t)L;
-            }
-        }
-        a.result[i] = res;
-        a.value[i] = v;
-        table_out[i] = tab;
-        level_out[i] = lev;
-        if constexpr (DB) db.src[i] = res == LSM_GET_ABSENT ? LSM_SRC_NONE : LSM_SRC_SSTABLE;
-    }
-}
-
-// lsm_search's kernel: its arguments are what they were before lsm_db_get
-__global__ __launch_bounds__(256) void search_kernel(GetArgs a, const McFile *files, SrShape S,
-                                                     int32_t *level_out, int32_t *table_out) {
-    search_body<false>(a, files, S, level_out, table_out, SrDb{});
-}
-
-__global__ __launch_bounds__(256) void db_search_kernel(GetArgs a, const McFile *files, SrShape S,
-                                                        int32_t *level_out, int32_t *table_out, SrDb db) {
-    search_body<true>(a, files, S, level_out, table_out, db);
 }
 
 template <int G>
@@ -3771,8 +2264,6 @@ extern "C" size_t lsm_build_sst_workspace_bytes(uint32_t nfile, uint32_t max_fil
         return (size_t)(4ull * kHashRecDwords * nfile * (uint64_t)max_file_records + 16);
     return (size_t)(kk * nfile * (uint64_t)max_file_records * 4 + 16);
 }
-
-static uint64_t barrett_recip(uint64_t m) { return ~0ull / m; }
 
 // The stream build's plan outputs (lsm_build_sst_stream): nfile is then the
 // bound nfile_max, the real count is *dnf on the device.
@@ -4122,409 +2613,6 @@ extern "C" int lsm_build_sst_stream(lsm_ctx *ctx, const uint8_t *d_keys, const u
     if (h[3]) return LSM_ESPACE;
     return build_sst_impl(ctx, d_keys, d_koff, d_vals, d_voff, d_file_start, (uint32_t)h[0], (uint32_t)h[1], m, k,
                           d_out, d_file_off, d_footer, w.rest, w.rest_bytes, stream, nullptr);
-}
-
-extern "C" int lsm_bloom_probe(lsm_ctx *ctx, const uint64_t *d_words, uint64_t m, uint32_t k,
-                               const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys,
-                               uint8_t *d_hit, void *stream) {
-    if (!ctx || m == 0 || m >= (1ull << 63)) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    if (!d_words || !d_keys || !d_koff || !d_hit) return LSM_EINVAL;
-    uint32_t grid = (uint32_t)((nkeys + 255) / 256);
-    hipLaunchKernelGGL(bloom_probe_kernel, dim3(grid), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_words, m, barrett_recip(m), k ? k : 1,
-                       d_keys, d_koff, nkeys, d_hit);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" size_t lsm_may_contain_workspace_bytes(uint32_t nfile, uint64_t nkeys) {
-    size_t t = 0;
-    mc_ws_layout(nullptr, nfile, nkeys, &t);
-    return t;
-}
-
-extern "C" int lsm_may_contain(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_off,
-                               const lsm_sst_meta *d_meta, uint32_t nfile, const uint8_t *d_keys,
-                               const uint64_t *d_koff, uint64_t nkeys, uint8_t *d_hit,
-                               void *d_workspace, size_t ws_bytes, void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nkeys == 0 || nfile == 0) return 0;
-    if (!d_img || !d_file_off || !d_meta || !d_keys || !d_koff || !d_hit || !d_workspace)
-        return LSM_EINVAL;
-    size_t need = 0;
-    const McWs w = mc_ws_layout(static_cast<uint8_t *>(d_workspace), nfile, nkeys, &need);
-    if (ws_bytes < need) return LSM_ESPACE;
-    const uint64_t grid = (nkeys + kMcThreads - 1) / kMcThreads;
-    if (grid > 0x7FFFFFFFull) return LSM_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (nkeys > 0xFFFFFFFFull) {  // list entries are 32-bit: the per-probe path
-        LSM_HIP_CHECK(hipMemsetAsync(w.flag, 0, 4, s));
-    } else {
-        hipLaunchKernelGGL(mc_prep_kernel, dim3(1), dim3(256), 0, s, d_img, d_file_off, d_meta, nfile, w);
-        // passes of up to 2M probes (the test kernel's segment table), as the
-        // level search runs them
-        const uint64_t pass = (uint64_t)kLvMaxWgs * kLvProbes;
-        for (uint64_t k0 = 0; k0 < nkeys; k0 += pass) {
-            const uint64_t n = nkeys - k0 < pass ? nkeys - k0 : pass;
-            const uint32_t nwg = (uint32_t)((n + kMcGroupProbes - 1) / kMcGroupProbes);
-            hipLaunchKernelGGL(mc_classify_kernel, dim3(nwg), dim3(kMcGroupThreads), 0, s, d_img, nfile,
-                               d_keys, d_koff, k0, k0 + n, w, nwg, d_hit);
-            hipLaunchKernelGGL(lv_test_kernel<true>, dim3(nfile), dim3(kLvThreads), kMcLdsBytes, s,
-                               d_img, nfile, nwg, w.lv, k0, d_hit, (const uint32_t *)w.flag);
-        }
-    }
-    const uint32_t pgrid = grid < kMcProbeGrid ? (uint32_t)grid : kMcProbeGrid;
-    hipLaunchKernelGGL(may_contain_kernel, dim3(pgrid), dim3(kMcThreads), 0, s, d_img,
-                       d_file_off, d_meta, nfile, d_keys, d_koff, nkeys, d_hit,
-                       (const uint32_t *)w.flag);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" size_t lsm_level_may_contain_workspace_bytes(uint32_t nfile, uint64_t nkeys) {
-    size_t total = 0;
-    lv_ws_layout(nullptr, nfile, nkeys, &total);
-    return total;
-}
-
-// The search over an index whose table array is `files` (lsm_level_index_build
-// output, or the workspace's own copy built just before).
-static int level_search(hipStream_t s, const uint8_t *d_img, const McFile *files, uint32_t nfile,
-                        const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys,
-                        int32_t *d_table, uint8_t *d_may, LvWs w) {
-    w.files = const_cast<McFile *>(files);
-    if (nfile > kLvMaxFiles || nkeys > 0xFFFFFFFFull) {
-        const uint64_t g = (nkeys + 255) / 256;
-        hipLaunchKernelGGL(lv_probe_kernel, dim3(g < 4096 ? (uint32_t)g : 4096u), dim3(256), 0, s,
-                           d_img, nfile, d_keys, d_koff, nkeys, w, d_table, d_may);
-    } else {
-        // passes of up to 2M probes (the test kernel's segment table)
-        const uint64_t pass = (uint64_t)kLvMaxWgs * kLvProbes;
-        for (uint64_t k0 = 0; k0 < nkeys; k0 += pass) {
-            const uint64_t n = nkeys - k0 < pass ? nkeys - k0 : pass;
-            const uint32_t nwg = (uint32_t)((n + kLvProbes - 1) / kLvProbes);
-            hipLaunchKernelGGL(lv_classify_kernel, dim3(nwg), dim3(kLvThreads), 0, s, d_img, nfile,
-                               d_keys, d_koff, k0, k0 + n, w, nwg, d_table, d_may);
-            hipLaunchKernelGGL(lv_test_kernel<false>, dim3(nfile), dim3(kLvThreads), kMcLdsBytes, s,
-                               d_img, nfile, nwg, w, k0, d_may, nullptr);
-        }
-    }
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lsm_level_may_contain(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_off,
-                                     const lsm_sst_meta *d_meta, uint32_t nfile,
-                                     const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys,
-                                     int32_t *d_table, uint8_t *d_may, void *d_workspace,
-                                     size_t ws_bytes, void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    if (!d_keys || !d_koff || !d_table || !d_may) return LSM_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (nfile == 0) {  // an empty level: no candidate (manager.go:194), nothing may be there
-        LSM_HIP_CHECK(hipMemsetAsync(d_table, 0xFF, 4 * nkeys, s));
-        LSM_HIP_CHECK(hipMemsetAsync(d_may, 0, nkeys, s));
-        return 0;
-    }
-    if (!d_img || !d_file_off || !d_meta || !d_workspace) return LSM_EINVAL;
-    size_t need = 0;
-    const LvWs w = lv_ws_layout(static_cast<uint8_t *>(d_workspace), nfile, nkeys, &need);
-    if (ws_bytes < need) return LSM_ESPACE;
-    hipLaunchKernelGGL(lv_prep_kernel, dim3((nfile + 255) / 256), dim3(256), 0, s, d_img, d_file_off,
-                       d_meta, nfile, w);
-    return level_search(s, d_img, w.files, nfile, d_keys, d_koff, nkeys, d_table, d_may, w);
-}
-
-extern "C" size_t lsm_level_index_bytes(uint32_t nfile) {
-    return sizeof(McFile) * (size_t)(nfile ? nfile : 1);
-}
-
-extern "C" int lsm_level_index_build(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_off,
-                                     const lsm_sst_meta *d_meta, uint32_t nfile, void *d_index,
-                                     void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nfile == 0) return 0;
-    if (!d_img || !d_file_off || !d_meta || !d_index) return LSM_EINVAL;
-    LvWs w{};
-    w.files = static_cast<McFile *>(d_index);
-    hipLaunchKernelGGL(lv_prep_kernel, dim3((nfile + 255) / 256), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), d_img, d_file_off, d_meta, nfile, w);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lsm_level_may_contain_indexed(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
-                                             uint32_t nfile, const uint8_t *d_keys,
-                                             const uint64_t *d_koff, uint64_t nkeys, int32_t *d_table,
-                                             uint8_t *d_may, void *d_workspace, size_t ws_bytes,
-                                             void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    if (!d_keys || !d_koff || !d_table || !d_may) return LSM_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (nfile == 0) {
-        LSM_HIP_CHECK(hipMemsetAsync(d_table, 0xFF, 4 * nkeys, s));
-        LSM_HIP_CHECK(hipMemsetAsync(d_may, 0, nkeys, s));
-        return 0;
-    }
-    if (!d_img || !d_index || !d_workspace) return LSM_EINVAL;
-    size_t need = 0;
-    const LvWs w = lv_ws_layout(static_cast<uint8_t *>(d_workspace), nfile, nkeys, &need);
-    if (ws_bytes < need) return LSM_ESPACE;
-    return level_search(s, d_img, static_cast<const McFile *>(d_index), nfile, d_keys, d_koff, nkeys,
-                        d_table, d_may, w);
-}
-
-static GetArgs get_args(const uint8_t *d_img, const uint64_t *d_file_off, const uint64_t *d_file_len,
-                        const lsm_sst_meta *d_meta, uint32_t nfile, const uint64_t *d_rec_base,
-                        const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value) {
-    GetArgs a{};
-    a.img = d_img;
-    a.file_off = d_file_off;
-    a.file_len = d_file_len;
-    a.meta = d_meta;
-    a.nfile = nfile;
-    a.rec_base = d_rec_base;
-    a.idx_desc = d_idx_desc;
-    a.idx_value = d_idx_value;
-    return a;
-}
-
-extern "C" size_t lsm_level_get_tree_bytes(uint32_t nfile, uint32_t max_nidx) {
-    return (size_t)nfile * tree_shape(max_nidx).blocks * 128;
-}
-
-extern "C" int lsm_level_get_tree_build(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_off,
-                                        const lsm_sst_meta *d_meta, uint32_t nfile,
-                                        const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc,
-                                        uint32_t max_nidx, void *d_tree, size_t tree_bytes,
-                                        void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    const TreeShape T = tree_shape(max_nidx);
-    if (nfile == 0 || T.D == 0) return 0;
-    if (!d_img || !d_file_off || !d_meta || !d_idx_desc || !d_tree) return LSM_EINVAL;
-    if (tree_bytes < lsm_level_get_tree_bytes(nfile, max_nidx)) return LSM_ESPACE;
-    GetArgs a = get_args(d_img, d_file_off, nullptr, d_meta, nfile, d_rec_base, d_idx_desc, nullptr);
-    a.tree_nidx = max_nidx;
-    a.tree_top = T.t;
-    a.tree_stride = T.blocks * 128;
-    const uint64_t grid = ((uint64_t)nfile * T.blocks * 8 + 255) / 256;
-    if (grid > 0x7FFFFFFFull) return LSM_EINVAL;
-    hipLaunchKernelGGL(get_tree_build_kernel, dim3((uint32_t)grid), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a, static_cast<uint8_t *>(d_tree), T);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// The Seek tree of a Get: it must span nfile tables of tree_nidx entries
-// (a tree built for fewer tables would be read past its end).
-static int get_tree_args(GetArgs &a, uint32_t nfile, const void *d_tree, uint32_t tree_nidx,
-                         size_t tree_bytes) {
-    const TreeShape T = tree_shape(tree_nidx);
-    if (!d_tree || !T.D) return 0;
-    if (tree_bytes < lsm_level_get_tree_bytes(nfile, tree_nidx)) return LSM_ESPACE;
-    a.tree = static_cast<const uint8_t *>(d_tree);
-    a.tree_nidx = tree_nidx;
-    a.tree_top = T.t;
-    a.tree_stride = T.blocks * 128;
-    return 0;
-}
-
-extern "C" int lsm_level_get(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_off,
-                             const uint64_t *d_file_len, const lsm_sst_meta *d_meta, uint32_t nfile,
-                             const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc,
-                             const int64_t *d_idx_value, const uint8_t *d_keys, const uint64_t *d_koff,
-                             uint64_t nkeys, const int32_t *d_table, const uint8_t *d_may,
-                             int32_t *d_result, lsm_rec_desc *d_value, const void *d_tree,
-                             uint32_t tree_nidx, size_t tree_bytes, void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    if (!d_keys || !d_koff || !d_table || !d_may || !d_result || !d_value) return LSM_EINVAL;
-    if (nfile && (!d_img || !d_file_off || !d_file_len || !d_meta || !d_idx_desc || !d_idx_value))
-        return LSM_EINVAL;
-    GetArgs a = get_args(d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc,
-                         d_idx_value);
-    a.keys = d_keys;
-    a.koff = d_koff;
-    a.nkeys = nkeys;
-    a.table = d_table;
-    a.may = d_may;
-    a.result = d_result;
-    a.value = d_value;
-    const int rc = get_tree_args(a, nfile, d_tree, tree_nidx, tree_bytes);
-    if (rc) return rc;
-    const uint64_t grid = (nkeys + 255) / 256;
-    if (grid > 0x7FFFFFFFull) return LSM_EINVAL;
-    hipLaunchKernelGGL(level_get_kernel, dim3((uint32_t)grid), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int lsm_level_search_get(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index, uint32_t nfile,
-                                    const uint64_t *d_file_off, const uint64_t *d_file_len,
-                                    const lsm_sst_meta *d_meta, const uint64_t *d_rec_base,
-                                    const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value,
-                                    const uint8_t *d_keys, const uint64_t *d_koff, uint64_t nkeys,
-                                    int32_t *d_table, uint8_t *d_may, int32_t *d_result, lsm_rec_desc *d_value,
-                                    const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
-                                    void *d_workspace, size_t ws_bytes, void *stream) {
-    // the level search (classify + per-table filter test), then the Get per
-    // probe at full occupancy: a Get inside the per-table test (its LDS
-    // refilled with the tree's top groups, one 1,024-thread workgroup per
-    // table) measured slower, 0.123-0.144 against 0.113 ms per 1M-key call
-    // 
-    const int rc = lsm_level_may_contain_indexed(ctx, d_img, d_index, nfile, d_keys, d_koff, nkeys, d_table,
-                                                 d_may, d_workspace, ws_bytes, stream);
-    if (rc) return rc;
-    return lsm_level_get(ctx, d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc, d_idx_value,
-                         d_keys, d_koff, nkeys, d_table, d_may, d_result, d_value, d_tree, tree_nidx, tree_bytes,
-                         stream);
-}
-
-extern "C" int lsm_level0_get(lsm_ctx *ctx, const uint8_t *d_img, const uint64_t *d_file_off,
-                              const uint64_t *d_file_len, const lsm_sst_meta *d_meta, uint32_t nfile,
-                              const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc,
-                              const int64_t *d_idx_value, const uint8_t *d_keys, const uint64_t *d_koff,
-                              uint64_t nkeys, int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value,
-                              const void *d_tree, uint32_t tree_nidx, size_t tree_bytes, void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    if (!d_keys || !d_koff || !d_table || !d_result || !d_value) return LSM_EINVAL;
-    if (nfile && (!d_img || !d_file_off || !d_file_len || !d_meta || !d_idx_desc || !d_idx_value))
-        return LSM_EINVAL;
-    GetArgs a = get_args(d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc,
-                         d_idx_value);
-    a.keys = d_keys;
-    a.koff = d_koff;
-    a.nkeys = nkeys;
-    a.result = d_result;
-    a.value = d_value;
-    const int rc = get_tree_args(a, nfile, d_tree, tree_nidx, tree_bytes);
-    if (rc) return rc;
-    const uint64_t grid = (nkeys + kL0Threads - 1) / kL0Threads;
-    if (grid > 0x7FFFFFFFull) return LSM_EINVAL;
-    hipLaunchKernelGGL(level0_get_kernel, dim3((uint32_t)grid), dim3(kL0Threads), 0,
-                       static_cast<hipStream_t>(stream), a, d_table);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-// The tree's shape from level_start; false when it does not start at 0 or decreases.
-static bool search_shape(const uint32_t *level_start, SrShape &S) {
-    for (uint32_t L = 0; L <= kSrLevels; L++) {
-        S.start[L] = level_start[L];
-        if (L && S.start[L] < S.start[L - 1]) return false;
-    }
-    return S.start[0] == 0;
-}
-
-// One thread per key holds its whole state: nothing per probe is kept between
-// launches, so the size depends on neither nkeys nor the tree.
-constexpr size_t kSrWsBytes = 256;
-
-extern "C" size_t lsm_search_workspace_bytes(const uint32_t *level_start, uint64_t nkeys) {
-    SrShape S{};
-    (void)nkeys;
-    if (!level_start || !search_shape(level_start, S) || S.start[kSrLevels] == 0) return 0;
-    return kSrWsBytes;
-}
-
-extern "C" int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
-                          const uint32_t *level_start, const uint64_t *d_file_off,
-                          const uint64_t *d_file_len, const lsm_sst_meta *d_meta,
-                          const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc,
-                          const int64_t *d_idx_value, const uint8_t *d_keys, const uint64_t *d_koff,
-                          uint64_t nkeys, int32_t *d_level, int32_t *d_table, int32_t *d_result,
-                          lsm_rec_desc *d_value, const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
-                          void *d_workspace, size_t ws_bytes, void *stream) {
-    if (!ctx) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    SrShape S{};
-    if (!level_start || !search_shape(level_start, S)) return LSM_EINVAL;
-    if (!d_keys || !d_koff || !d_level || !d_table || !d_result || !d_value) return LSM_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t nfile = S.start[kSrLevels];
-    if (nfile == 0) {  // an empty tree: every key absent
-        LSM_HIP_CHECK(hipMemsetAsync(d_level, 0xFF, 4 * nkeys, s));
-        LSM_HIP_CHECK(hipMemsetAsync(d_table, 0xFF, 4 * nkeys, s));
-        LSM_HIP_CHECK(hipMemsetAsync(d_result, 0, 4 * nkeys, s));
-        LSM_HIP_CHECK(hipMemsetAsync(d_value, 0, sizeof(lsm_rec_desc) * nkeys, s));
-        return 0;
-    }
-    if (!d_img || !d_index || !d_file_off || !d_file_len || !d_meta || !d_idx_desc || !d_idx_value ||
-        !d_workspace)
-        return LSM_EINVAL;
-    if (ws_bytes < kSrWsBytes) return LSM_ESPACE;
-    GetArgs a = get_args(d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc,
-                         d_idx_value);
-    a.keys = d_keys;
-    a.koff = d_koff;
-    a.nkeys = nkeys;
-    a.result = d_result;
-    a.value = d_value;
-    const int rc = get_tree_args(a, nfile, d_tree, tree_nidx, tree_bytes);
-    if (rc) return rc;
-    const McFile *files = static_cast<const McFile *>(d_index);
-    const uint64_t g = (nkeys + 255) / 256;
-    const dim3 grid(g < kSrMaxGrid ? (uint32_t)g : kSrMaxGrid);
-    hipLaunchKernelGGL(search_kernel, grid, dim3(256), 0, s, a, files, S, d_level, d_table);
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
-}
-
-extern "C" size_t lsm_db_get_workspace_bytes(const uint32_t *level_start, uint64_t nkeys) {
-    return lsm_search_workspace_bytes(level_start, nkeys);
-}
-
-extern "C" int lsm_db_get(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
-                          const uint32_t *d_idx, const uint64_t *d_file_start, uint32_t nlog,
-                          const void *d_mem_index, size_t mem_index_bytes, const uint8_t *d_img,
-                          const void *d_index, const uint32_t *level_start, const uint64_t *d_file_off,
-                          const uint64_t *d_file_len, const lsm_sst_meta *d_meta, const uint64_t *d_rec_base,
-                          const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value, const void *d_tree,
-                          uint32_t tree_nidx, size_t tree_bytes, const uint8_t *d_keys,
-                          const uint64_t *d_koff, uint64_t nkeys, int mode, int32_t *d_mem_result,
-                          int32_t *d_log, uint32_t *d_slot, int32_t *d_level, int32_t *d_table,
-                          int32_t *d_result, lsm_rec_desc *d_value, int32_t *d_src, void *d_workspace,
-                          size_t ws_bytes, void *stream) {
-    if (!ctx || (mode != LSM_DBGET_EXACT && mode != LSM_DBGET_TOMBSTONE_HIDES)) return LSM_EINVAL;
-    if (nkeys == 0) return 0;
-    SrShape S{};
-    if (!level_start || !search_shape(level_start, S)) return LSM_EINVAL;
-    if (!d_keys || !d_koff || !d_level || !d_table || !d_result || !d_value || !d_src) return LSM_EINVAL;
-    const uint32_t nfile = S.start[kSrLevels];
-    // an empty tree needs none of the tree's buffers: every level of S is empty
-    // and the kernel reads no table
-    GetArgs a{};
-    if (nfile) {
-        if (!d_img || !d_index || !d_file_off || !d_file_len || !d_meta || !d_idx_desc || !d_idx_value ||
-            !d_workspace)
-            return LSM_EINVAL;
-        if (ws_bytes < kSrWsBytes) return LSM_ESPACE;
-        a = get_args(d_img, d_file_off, d_file_len, d_meta, nfile, d_rec_base, d_idx_desc, d_idx_value);
-        const int rc = get_tree_args(a, nfile, d_tree, tree_nidx, tree_bytes);
-        if (rc) return rc;
-    }
-    a.keys = d_keys;
-    a.koff = d_koff;
-    a.nkeys = nkeys;
-    a.result = d_result;
-    a.value = d_value;
-    // every check of both halves is made before the first launch
-    const int rc = lsm_memtable_search(ctx, d_bytes, d_desc, d_idx, d_file_start, nlog, d_mem_index,
-                                       mem_index_bytes, d_keys, d_koff, nkeys, d_mem_result, d_log, d_slot,
-                                       d_value, stream);
-    if (rc) return rc;
-    const uint64_t g = (nkeys + 255) / 256;
-    const dim3 grid(g < kSrMaxGrid ? (uint32_t)g : kSrMaxGrid);
-    hipLaunchKernelGGL(db_search_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a,
-                       static_cast<const McFile *>(d_index), S, d_level, d_table,
-                       SrDb{d_mem_result, d_src, mode});
-    LSM_HIP_CHECK(hipGetLastError());
-    return 0;
 }
 
 extern "C" int lsm_sum256(lsm_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_koff,

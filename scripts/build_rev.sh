@@ -6,8 +6,10 @@ ROOT=$(cd $(dirname $0)/.. && pwd)
 W=$(mktemp -d /tmp/rev.XXXX)
 (cd $ROOT && git archive $1 go-lsm_amd/csrc include | tar -x -C $W)
 pids=""
-for f in api decode encode merge; do
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$W/include -I$W/go-lsm_amd/csrc -c $W/go-lsm_amd/csrc/$f.hip -o $W/$f.o &
+# every translation unit the revision has (the set differs between revisions)
+for src in $W/go-lsm_amd/csrc/*.hip; do
+  f=$(basename $src .hip)
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$W/include -I$W/go-lsm_amd/csrc -c $src -o $W/$f.o &
   pids="$pids $!"
 done
 for p in $pids; do wait $p; done

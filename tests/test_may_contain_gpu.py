@@ -198,6 +198,46 @@ def test_may_contain_sorted_shared_long_prefixes(ctx):
     check(ctx, rng, images, probes)
 
 
+def _bound_tables(base):
+    """Ten bounds in key order over one 17-byte base: lengths 0, 1, 7, 8, 9,
+    15, 16 and 17, four of them another bound plus a 0x00 byte (what zero
+    padding of a 16-byte prefix hides).  -> (overlapping tables in no key
+    order, the same bounds as five disjoint tables in key order)."""
+    b = [b"", base[:1], base[:7], base[:7] + b"\x00", base[:8], base[:8] + b"\x00", base[:15],
+         base[:15] + b"\x00", base[:16], base[:17]]
+    assert all(x < y for x, y in zip(b, b[1:]))
+    assert {len(x) for x in b} == {0, 1, 7, 8, 9, 15, 16, 17}
+    overlapping = [(b[6], b[9]), (b[0], b[4]), (b[3], b[7]), (b[1], b[8]), (b[2], b[5])]
+    disjoint = [(b[2 * i], b[2 * i + 1]) for i in range(5)]
+    return b, overlapping, disjoint
+
+
+def test_may_contain_bound_lengths_around_the_prefix(ctx):
+    """Bounds shorter than, equal to and longer than the 16-byte prefix the
+    kernels compare first, some ending in 0x00 and some equal to another
+    table's bound plus 0x00, on the per-probe path (five overlapping tables
+    in no key order) and on the grouped path (five disjoint tables in key
+    order).  Probes: every bound of both sets, each with 0x00 appended and
+    with its last byte dropped, and the empty key; every (probe, table) pair
+    against the oracle."""
+    rng = np.random.default_rng(91)
+    ba, overlapping, _ = _bound_tables(b"abcdefghijklmnopq")
+    bz, _, disjoint = _bound_tables(b"abcDEFGHIJKLMNOPQ")
+    probes = [b""]
+    for x in ba + bz:
+        probes += [x, x + b"\x00", x[:-1]]  # 61 probes, 34 distinct keys
+    # k = 0: Test is true, so the range check alone decides every pair (a
+    # sparse filter would hide a key admitted by mistake); then a real filter
+    for m, k in ((64, 0), (1024, 3)):
+        for tables in (overlapping, disjoint):
+            images = [build([lo, hi], m=m, k=k) for lo, hi in tables]
+            for im, (lo, hi) in zip(images, tables):
+                assert _file(im)[1:3] == (lo, hi)
+            if k == 0:  # not vacuous: both answers occur for every table
+                assert all({expected(im, p) for p in probes} == {0, 1} for im in images)
+            check(ctx, rng, images, probes)
+
+
 def _patch_nbits(img, nbits):
     """The image with its stored bitset length (the u64be after m and k,
     bloom.go:239-250 / bitset.ReadFrom) lowered: the filter block keeps its
