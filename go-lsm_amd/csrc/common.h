@@ -35,6 +35,19 @@ struct lsm_ctx {
 };
 constexpr size_t kHostReadback = 256 * 1024;
 
+// Carves a workspace into 256-byte aligned arrays; over a null base it only
+// sizes (`at` ends as the bytes needed).
+struct WsCursor {
+    uint8_t *base;
+    size_t at;
+    template <class T>
+    T *take(size_t n) {
+        T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
+        at += (sizeof(T) * n + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
 namespace lsm {
 
 constexpr int kWave = 64;
@@ -159,6 +172,17 @@ __device__ __forceinline__ uint64_t wave_excl_scan64(uint64_t v, uint64_t *total
     *total = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(inc >> 32), kWave - 1) << 32 |
              (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)inc, kWave - 1);
     return inc - v;
+}
+
+// The largest value over the wave (lane 0 holds it, as every lane).
+__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const uint64_t o = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d) << 32 |
+                           (uint32_t)__shfl_xor((int)(uint32_t)v, d);
+        v = o > v ? o : v;
+    }
+    return v;
 }
 
 // Copy `len` bytes from buffer offset `src` (rsrc-relative, any alignment)

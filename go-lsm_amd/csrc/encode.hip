@@ -21,6 +21,7 @@
 #include "common.h"
 #include "hashrec.h"
 #include "murmur.h"
+#include "scan.h"
 
 namespace lsm {
 namespace {
@@ -1331,47 +1332,6 @@ __device__ __forceinline__ void seg_barrier() {
     __asm__ __volatile__("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-struct SegPair {
-    uint64_t s, c;
-};
-
-// Exclusive sums of two values over the plan kernel's 1,024 threads.
-__device__ __forceinline__ SegPair seg_block_scan2(uint64_t s, uint64_t c, SegPair *total) {
-    constexpr uint32_t NW = kSegThreads / kWave;
-    __shared__ uint64_t ws_[NW], wc_[NW];
-    uint64_t ts, tc;
-    const uint64_t xs = wave_excl_scan64(s, &ts), xc = wave_excl_scan64(c, &tc);
-    const uint32_t w = threadIdx.x / kWave;
-    if (lane_id() == 0) {
-        ws_[w] = ts;
-        wc_[w] = tc;
-    }
-    seg_barrier();
-    uint64_t ps = 0, pc = 0, as = 0, ac = 0;
-    for (uint32_t i = 0; i < NW; i++) {
-        if (i < w) {
-            ps += ws_[i];
-            pc += wc_[i];
-        }
-        as += ws_[i];
-        ac += wc_[i];
-    }
-    seg_barrier();
-    *total = SegPair{as, ac};
-    return SegPair{ps + xs, pc + xc};
-}
-
-// The largest value over the wave (lane 0 holds it, as every lane).
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t o = (uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d) << 32 |
-                           (uint32_t)__shfl_xor((int)(uint32_t)v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 __device__ __forceinline__ uint64_t est_at(const uint64_t *koff, const uint64_t *voff, uint64_t t) {
     return 16 * t + koff[t] + voff[t];
 }
@@ -1640,8 +1600,9 @@ __global__ __launch_bounds__(kSegThreads) void sst_stream_plan_kernel(StreamPlan
         }
         const uint64_t nsp = (nr + kRegSpanRecs - 1) / kRegSpanRecs;
         if (f == 0) s_nsp0 = (uint32_t)nsp;
-        SegPair tot;
-        const SegPair x = seg_block_scan2((sz + a.align - 1) / a.align * a.align, nsp, &tot);
+        Sum2 tot;
+        const Sum2 x = wg_excl_scan<kSegThreads, seg_barrier>(
+            Sum2{(sz + a.align - 1) / a.align * a.align, nsp}, &tot);
         if (f < nfile) {
             const uint64_t off = s_carry + x.s;
             a.file_off[f] = off;

@@ -372,19 +372,6 @@ struct McWs {
     LvWs lv;            // the probes grouped by candidate file, as the level search's
 };
 
-// Carves a workspace into 256-byte aligned arrays; over a null base it only
-// sizes (`at` ends as the bytes needed).
-struct WsCursor {
-    uint8_t *base;
-    size_t at;
-    template <class T>
-    T *take(size_t n) {
-        T *p = base ? reinterpret_cast<T *>(base + at) : nullptr;
-        at += (sizeof(T) * n + 255) & ~(size_t)255;
-        return p;
-    }
-};
-
 LvWs lv_ws_layout(WsCursor &c, uint32_t nfile, uint64_t nkeys) {
     LvWs w{};
     const uint64_t pass = nkeys < (uint64_t)kLvMaxWgs * kLvProbes ? nkeys : (uint64_t)kLvMaxWgs * kLvProbes;
@@ -442,7 +429,7 @@ __device__ __forceinline__ void lv_load_keys(const uint8_t *keys, const uint64_t
 
 // Exclusive prefix sum of v over the kLvThreads-thread block through the LDS
 // row `part`, which is left holding the inclusive sums (part[kLvThreads - 1]:
-// the total).
+// the total).  Not scan.h's wave-sum scan: the classify kernels read the row back.
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t *part, uint32_t v) {
     const uint32_t t = threadIdx.x;
     part[t] = v;

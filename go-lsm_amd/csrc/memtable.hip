@@ -527,23 +527,17 @@ struct Ws {
     uint32_t *blkcnt, *total, *lead, *cut;
 };
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 uint32_t blocks_per_log(uint32_t maxrec) { return (maxrec + kThreads - 1) / kThreads; }
 
-size_t ws_layout(uint8_t *p, uint32_t nlog, uint64_t nslot, uint32_t maxrec, Ws *w) {
-    const size_t s8 = align256(16 * nslot), s4 = align256(4 * nslot);  // s8: one Key16 buffer
-    const size_t sb = align256(4 * (size_t)nlog * blocks_per_log(maxrec)), sl = align256(4 * (size_t)nlog);
-    if (w) {
-        w->key[0] = reinterpret_cast<Key16 *>(p);
-        w->key[1] = reinterpret_cast<Key16 *>(p + s8);
-        w->pos[0] = reinterpret_cast<uint32_t *>(p + 2 * s8);
-        w->pos[1] = reinterpret_cast<uint32_t *>(p + 2 * s8 + s4);
-        w->blkcnt = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4);
-        w->total = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4 + sb);
-        w->lead = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4 + sb + sl);
-        w->cut = reinterpret_cast<uint32_t *>(p + 2 * s8 + 2 * s4 + sb + 2 * sl);
-    }
-    return 2 * s8 + 2 * s4 + sb + 3 * sl;
+Ws ws_layout(WsCursor &c, uint32_t nlog, uint64_t nslot, uint32_t maxrec) {
+    Ws w;
+    for (int i = 0; i < 2; i++) w.key[i] = c.take<Key16>(nslot);
+    for (int i = 0; i < 2; i++) w.pos[i] = c.take<uint32_t>(nslot);
+    w.blkcnt = c.take<uint32_t>((size_t)nlog * blocks_per_log(maxrec));
+    w.total = c.take<uint32_t>(nlog);
+    w.lead = c.take<uint32_t>(nlog);
+    w.cut = c.take<uint32_t>(nlog);
+    return w;
 }
 
 }  // namespace
@@ -551,7 +545,9 @@ size_t ws_layout(uint8_t *p, uint32_t nlog, uint64_t nslot, uint32_t maxrec, Ws 
 extern "C" size_t lsm_memtable_order_workspace_bytes(uint32_t nlog, uint64_t nslot,
                                                      uint32_t max_log_records) {
     if (nlog == 0) return 0;
-    return ws_layout(nullptr, nlog, nslot, max_log_records, nullptr);
+    WsCursor c{nullptr, 0};
+    ws_layout(c, nlog, nslot, max_log_records);
+    return c.at;
 }
 
 extern "C" int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_desc,
@@ -570,8 +566,8 @@ extern "C" int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const ls
     if (!d_ws || ws_bytes < lsm_memtable_order_workspace_bytes(nlog, nslot, max_log_records))
         return LSM_ESPACE;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    Ws ws;
-    ws_layout(static_cast<uint8_t *>(d_ws), nlog, nslot, max_log_records, &ws);
+    WsCursor c{static_cast<uint8_t *>(d_ws), 0};
+    const Ws ws = ws_layout(c, nlog, nslot, max_log_records);
     // with no slot or no admitted record every log is empty (or overflows)
     const Logs L{d_bytes, d_desc, d_rec_base, d_log_off, d_nrec, d_status, nlog, (uint32_t)nslot,
                  nslot ? max_log_records : 0};

@@ -44,6 +44,7 @@
 #include <vector>
 
 #include "common.h"
+#include "scan.h"
 
 namespace lsm {
 namespace {
@@ -53,8 +54,7 @@ constexpr uint32_t kStatBlocks = 1024;
 constexpr uint32_t kFastChunks = 4;               // chunks counted in the first pass (32 B keys)
 constexpr uint32_t kMaxChunks = kKeyCap / 8 + 1;  // 1 MiB keys
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr uint32_t kScanPer = 2;  // 16: lanes 256 B apart (strided stores); A/B compact 1.359 -> 1.348 ms
-constexpr uint32_t kScanTile = kMergeThreads * kScanPer;
+static_assert(kMergeThreads == kScanThreads, "the per-tile scan kernels run kScanTile values a workgroup");
 constexpr uint32_t kMergePathMin = 4096;  // fewer pairs: the radix passes alone
 
 // Go's kv.DeletedValue, "～DELETED～" (kv/kv.go:29), 13 bytes
@@ -120,13 +120,6 @@ __device__ __forceinline__ uint64_t wave_and64(uint64_t v) {
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t l) {
     return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l) << 32 |
            (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
-}
-__device__ __forceinline__ uint64_t wave_max64(uint64_t v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint64_t t = __shfl_xor(v, o);
-        v = t > v ? t : v;
-    }
-    return v;
 }
 __device__ __forceinline__ uint64_t wave_min64(uint64_t v) {
     for (int o = 32; o > 0; o >>= 1) {
@@ -466,7 +459,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_flags_kernel(MergeIn m, c
 // eq[j] = 1 when sorted position j holds the same key as j - 1 (plain key
 // equality: for container/heap "" equals "", merge.go:21-23's Less is key <)
 // LSM_TIE_GOHEAP's dense key ranks, on the device: newg[j] = 1 where sorted
-// position j starts a new key (merge_scan_tiles / merge_scan_partials then
+// position j starts a new key (merge_scan_tiles / scan_partials_kernel then
 // give each tile its first rank), and goheap_rank_apply writes each pair's
 // rank by input index -- the only array the host's heap replay reads.
 __global__ __launch_bounds__(kMergeThreads) void goheap_newgroup_kernel(MergeIn m, const uint32_t *perm,
@@ -499,36 +492,10 @@ __global__ __launch_bounds__(kMergeThreads) void merge_candidate_kernel(MergeIn 
 
 // ---- interleaved exclusive sums of candidate sizes and counts -----------
 
-struct SumPair {
-    uint64_t s, c;  // bytes and candidates before position j
-};
-
-__device__ __forceinline__ SumPair block_excl_scan2(uint64_t s, uint64_t c, SumPair *total) {
-    __shared__ uint64_t ws_[kMergeThreads / kWave], wc_[kMergeThreads / kWave];
-    uint64_t ts, tc;
-    const uint64_t xs = wave_excl_scan64(s, &ts), xc = wave_excl_scan64(c, &tc);
-    const uint32_t w = threadIdx.x / kWave;
-    if (lane_id() == 0) {
-        ws_[w] = ts;
-        wc_[w] = tc;
-    }
-    __syncthreads();
-    uint64_t ps = 0, pc = 0, as = 0, ac = 0;
-    for (uint32_t i = 0; i < kMergeThreads / kWave; i++) {
-        if (i < w) {
-            ps += ws_[i];
-            pc += wc_[i];
-        }
-        as += ws_[i];
-        ac += wc_[i];
-    }
-    __syncthreads();
-    *total = SumPair{as, ac};
-    return SumPair{xs + ps, xc + pc};
-}
+// Sum2 (scan.h): s the bytes and c the candidates before position j.
 
 __global__ __launch_bounds__(kMergeThreads) void merge_scan_tiles(const uint32_t *csize, uint32_t n,
-                                                                  SumPair *part) {
+                                                                  Sum2 *part) {
     uint64_t s = 0, c = 0;
     const uint64_t i0 = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * kScanPer;
     for (uint32_t t = 0; t < kScanPer; t++) {
@@ -536,64 +503,13 @@ __global__ __launch_bounds__(kMergeThreads) void merge_scan_tiles(const uint32_t
         s += v;
         c += v != 0;
     }
-    SumPair tot;
-    block_excl_scan2(s, c, &tot);
+    Sum2 tot;
+    wg_excl_scan<kMergeThreads>(Sum2{s, c}, &tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
-// one pass over the tile sums by 1,024 threads (see plan_scan_partials): a
-// contiguous stretch per thread, one block scan of the stretch sums
-constexpr uint32_t kPartThreads = 1024;
-
-__global__ __launch_bounds__(kPartThreads) void merge_scan_partials(SumPair *part, uint32_t ntiles,
-                                                                    SumPair *sc, uint32_t n) {
-    __shared__ uint64_t ws_[kPartThreads / kWave], wc_[kPartThreads / kWave];
-    const uint32_t per = (ntiles + kPartThreads - 1) / kPartThreads, b = threadIdx.x * per;
-    const uint32_t e = b + per < ntiles ? b + per : ntiles;
-    uint64_t s = 0, c = 0;
-    for (uint32_t i0 = b; i0 < e; i0 += 8) {  // 8 loads in flight
-        SumPair v[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) v[k] = i0 + k < e ? part[i0 + k] : SumPair{0, 0};
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) {
-            s += v[k].s;
-            c += v[k].c;
-        }
-    }
-    uint64_t ts, tc;
-    const uint64_t xs = wave_excl_scan64(s, &ts), xc = wave_excl_scan64(c, &tc);
-    const uint32_t w = threadIdx.x / kWave;
-    if (lane_id() == 0) {
-        ws_[w] = ts;
-        wc_[w] = tc;
-    }
-    __syncthreads();
-    SumPair pre{xs, xc}, tot{0, 0};
-    for (uint32_t i = 0; i < kPartThreads / kWave; i++) {
-        if (i < w) {
-            pre.s += ws_[i];
-            pre.c += wc_[i];
-        }
-        tot.s += ws_[i];
-        tot.c += wc_[i];
-    }
-    for (uint32_t i0 = b; i0 < e; i0 += 8) {
-        SumPair v[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) v[k] = i0 + k < e ? part[i0 + k] : SumPair{0, 0};
-#pragma unroll
-        for (uint32_t k = 0; k < 8; k++) {
-            if (i0 + k < e) part[i0 + k] = pre;
-            pre.s += v[k].s;
-            pre.c += v[k].c;
-        }
-    }
-    if (threadIdx.x == 0) sc[n] = tot;
-}
-
 __global__ __launch_bounds__(kMergeThreads) void goheap_rank_apply(const uint32_t *newg, uint32_t n,
-                                                                   const SumPair *part,
+                                                                   const Sum2 *part,
                                                                    const uint32_t *perm,
                                                                    uint32_t *rank) {
     uint32_t f[kScanPer];
@@ -603,8 +519,8 @@ __global__ __launch_bounds__(kMergeThreads) void goheap_rank_apply(const uint32_
         f[t] = i0 + t < n ? newg[i0 + t] : 0u;
         s += f[t];
     }
-    SumPair tot;
-    const SumPair x = block_excl_scan2(s, 0, &tot);
+    Sum2 tot;
+    const Sum2 x = wg_excl_scan<kMergeThreads>(Sum2{s, 0}, &tot);
     uint64_t g = x.s + part[blockIdx.x].s;
     for (uint32_t t = 0; t < kScanPer; t++) {
         g += f[t];  // inclusive: the rank of position i0 + t
@@ -624,7 +540,7 @@ __global__ __launch_bounds__(kMergeThreads) void goheap_rank_apply(const uint32_
 constexpr uint32_t kExtScan = 254;
 
 __global__ __launch_bounds__(kMergeThreads) void merge_scan_apply(const uint32_t *csize, uint32_t n,
-                                                                  const SumPair *part, SumPair *sc,
+                                                                  const Sum2 *part, Sum2 *sc,
                                                                   const uint8_t *flags, MergeIn m,
                                                                   const uint32_t *perm, const uint64_t *xinfo,
                                                                   uint64_t *cand_pn,
@@ -637,11 +553,11 @@ __global__ __launch_bounds__(kMergeThreads) void merge_scan_apply(const uint32_t
         s += v[t];
         c += v[t] != 0;
     }
-    SumPair tot;
-    const SumPair x = block_excl_scan2(s, c, &tot);
+    Sum2 tot;
+    const Sum2 x = wg_excl_scan<kMergeThreads>(Sum2{s, c}, &tot);
     uint64_t ps = x.s + part[blockIdx.x].s, pc = x.c + part[blockIdx.x].c;
     for (uint32_t t = 0; t < kScanPer; t++) {
-        if (i0 + t < n) sc[i0 + t] = SumPair{ps, pc};
+        if (i0 + t < n) sc[i0 + t] = Sum2{ps, pc};
         if (v[t]) {
             const uint64_t k = i0 + t;
             const bool cont = k + 1 < n && !(flags[k + 1] & 1);
@@ -688,7 +604,7 @@ struct WalkArgs {
     MergeIn m;
     const uint32_t *perm;
     const uint8_t *flags;
-    const SumPair *sc;  // n + 1
+    const Sum2 *sc;  // n + 1
     const uint64_t *cand_pn;   // per candidate: the size sum after it
     const uint32_t *cand_pos;  // per candidate: its position | continues << 31
     const uint64_t *cand_ext;  // per continuing candidate: the next file's extra (merge_scan_apply)
@@ -799,7 +715,7 @@ struct AbsArgs {
     const uint64_t *cand_pn;
     const uint32_t *cand_pos;
     const uint64_t *cand_ext;
-    const SumPair *sc;
+    const Sum2 *sc;
     uint32_t n;
     uint64_t threshold;
     uint8_t *succ;    // [kAbsMaxWin][kAbsW]
@@ -807,12 +723,12 @@ struct AbsArgs {
     uint32_t *head;   // [0] = windows, [1] = file 0's end in window 0 (or a code)
 };
 
-__device__ __forceinline__ uint32_t abs_windows(const SumPair &tail, uint64_t T) {
+__device__ __forceinline__ uint32_t abs_windows(const Sum2 &tail, uint64_t T) {
     if (tail.c == 0) return 0;
     const uint64_t nf = tail.s / T + 2;
     return nf < kAbsMaxWin ? (uint32_t)nf : kAbsMaxWin;
 }
-__device__ __forceinline__ uint64_t abs_base(const SumPair &tail, uint64_t T, uint32_t f) {
+__device__ __forceinline__ uint64_t abs_base(const Sum2 &tail, uint64_t T, uint32_t f) {
     const double span = ((double)T + 0.5 * (double)tail.s / (double)tail.c) * (double)tail.c / (double)tail.s;
     const uint64_t c = (uint64_t)((double)(f + 1) * span + 0.5);
     return c > 1 + kAbsW / 2 ? c - kAbsW / 2 : 1;
@@ -822,7 +738,7 @@ __global__ __launch_bounds__(kAbsThreads) void merge_walk_abs_kernel(AbsArgs a) 
     __shared__ uint64_t np[kAbsW];
     __shared__ uint32_t s_first;
     const uint32_t f = blockIdx.x, t = threadIdx.x;
-    const SumPair tail = a.sc[a.n];
+    const Sum2 tail = a.sc[a.n];
     const uint64_t T = a.threshold;
     const uint32_t nwin = abs_windows(tail, T), ncand = (uint32_t)tail.c;
     if (f == 0 && t == 0) a.head[0] = nwin;
@@ -890,7 +806,7 @@ __global__ __launch_bounds__(kWalkThreads) void merge_walk_kernel(WalkArgs a) {
     __shared__ uint32_t s_q0;
     __shared__ uint64_t s_x0;
     const uint32_t n = a.m.n, t = threadIdx.x, lane = lane_id(), wave = t / kWave;
-    const SumPair tail = a.sc[n];
+    const Sum2 tail = a.sc[n];
     const uint64_t T = a.threshold;
     const uint32_t ncand = (uint32_t)tail.c;
     if (t == 0) {
@@ -1194,7 +1110,7 @@ __global__ __launch_bounds__(kWalkThreads) void merge_walk_kernel(WalkArgs a) {
                 end = lo;  // the first position at or above the target; e = end - 1
             }
         }
-        const SumPair Se = end < n ? a.sc[end] : tail;
+        const Sum2 Se = end < n ? a.sc[end] : tail;
         const uint64_t nw = (w != kNone ? 1 : 0) + (end > g ? Se.c - Cg : 0);
         if (t == 0) {
             WalkState x = S0;
@@ -1228,7 +1144,7 @@ __global__ __launch_bounds__(kWalkThreads) void merge_walk_kernel(WalkArgs a) {
 // each candidate's output slot: its file's first slot, after the extra, plus
 // the candidates before it in the file
 __global__ __launch_bounds__(kMergeThreads) void merge_emit_kernel(
-    const uint32_t *perm, const SumPair *sc, const uint32_t *csize, const MergeFile *files,
+    const uint32_t *perm, const Sum2 *sc, const uint32_t *csize, const MergeFile *files,
     const uint64_t *counts, uint32_t n, uint32_t *out, uint64_t *file_start, uint64_t *counts_out) {
     __shared__ uint32_t s_lo;
     const uint32_t j0 = blockIdx.x * kMergeThreads, j = j0 + threadIdx.x;
@@ -1263,7 +1179,7 @@ __global__ __launch_bounds__(kMergeThreads) void merge_emit_kernel(
 
 // The gather's key / value offsets: one scan of the selected pairs' (key
 // length, value length) -- tile sums (the lengths kept), the tile sums'
-// scan (merge_scan_partials), then each slot's offsets -- where two scans
+// scan (scan_partials_kernel), then each slot's offsets -- where two scans
 // of separately gathered lengths took 88 us for 3.3M pairs.
 // the gather's pair count: the host's, or lsm_gather_kvs_dev's device count,
 // capped at the bound the grid and the klen / vlen / koff / voff arrays are
@@ -1283,7 +1199,7 @@ __device__ __forceinline__ uint32_t gather_count(uint32_t nmax, const uint64_t *
 __global__ __launch_bounds__(kMergeThreads) void gather_scan_tiles(MergeIn m, const uint32_t *idx,
                                                                    uint32_t nmax, const uint64_t *d_nout,
                                                                    uint32_t *klen, uint32_t *vlen,
-                                                                   SumPair *part, uint64_t *ksrc) {
+                                                                   Sum2 *part, uint64_t *ksrc) {
     const uint32_t nout = gather_count(nmax, d_nout);
     uint64_t s = 0, c = 0;
     const uint64_t i0 = (uint64_t)blockIdx.x * kScanTile + threadIdx.x * kScanPer;
@@ -1297,16 +1213,16 @@ __global__ __launch_bounds__(kMergeThreads) void gather_scan_tiles(MergeIn m, co
             c += v.vl;
         }
     }
-    SumPair tot;
-    block_excl_scan2(s, c, &tot);
+    Sum2 tot;
+    wg_excl_scan<kMergeThreads>(Sum2{s, c}, &tot);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(kMergeThreads) void gather_scan_apply(const uint32_t *klen,
                                                                    const uint32_t *vlen, uint32_t nmax,
                                                                    const uint64_t *d_nout,
-                                                                   const SumPair *part,
-                                                                   const SumPair *total, uint64_t *koff,
+                                                                   const Sum2 *part,
+                                                                   const Sum2 *total, uint64_t *koff,
                                                                    uint64_t *voff) {
     const uint32_t nout = gather_count(nmax, d_nout);
     uint32_t kl[kScanPer], vl[kScanPer];
@@ -1318,8 +1234,8 @@ __global__ __launch_bounds__(kMergeThreads) void gather_scan_apply(const uint32_
         s += kl[t];
         c += vl[t];
     }
-    SumPair tot;
-    const SumPair x = block_excl_scan2(s, c, &tot);
+    Sum2 tot;
+    const Sum2 x = wg_excl_scan<kMergeThreads>(Sum2{s, c}, &tot);
     uint64_t ps = x.s + part[blockIdx.x].s, pc = x.c + part[blockIdx.x].c;
     for (uint32_t t = 0; t < kScanPer; t++) {
         if (i0 + t < nout) {
@@ -1537,8 +1453,8 @@ __global__ __launch_bounds__(kMergeThreads) void sst_layout_kernel(const uint64_
             sz = hdr + filter + 4 * nr + (voff[r1] - voff[r0]) + 12 * nr + (koff[r1] - koff[r0]) + 32;
             size[f] = sz;
         }
-        SumPair tot;
-        const SumPair x = block_excl_scan2((sz + align - 1) / align * align, 0, &tot);
+        Sum2 tot;
+        const Sum2 x = wg_excl_scan<kMergeThreads>(Sum2{(sz + align - 1) / align * align, 0}, &tot);
         if (f < nfile) file_off[f] = carry + x.s;
         carry += tot.s;
     }
@@ -1560,8 +1476,8 @@ __global__ __launch_bounds__(kMergeThreads) void sst_pairs_scan_kernel(const lsm
     for (uint32_t f0 = 0; f0 < nfile; f0 += kMergeThreads) {
         const uint32_t f = f0 + threadIdx.x;
         const uint64_t c = f < nfile ? sst_pair_count(meta[f]) : 0;
-        SumPair tot;
-        const SumPair x = block_excl_scan2(c, 0, &tot);
+        Sum2 tot;
+        const Sum2 x = wg_excl_scan<kMergeThreads>(Sum2{c, 0}, &tot);
         if (f < nfile) prefix[f] = carry + x.s;
         carry += tot.s;
     }
@@ -1588,8 +1504,8 @@ struct MergeWs {
     uint64_t *keys[2];
     uint8_t *flags;
     uint32_t *csize;
-    SumPair *sc;
-    SumPair *scan_part;
+    Sum2 *sc;
+    Sum2 *scan_part;
     MergeFile *files;
     uint64_t *stats;  // [0..1] counts, then the long-key OR/AND words
     uint64_t *part;   // kStatBlocks * kStatWords
@@ -1613,32 +1529,27 @@ size_t sort_tmp_bytes(uint32_t n) {
 
 MergeWs merge_ws_layout(uint8_t *base, uint32_t n) {
     MergeWs w{};
-    size_t at = 0;
-    auto take = [&](size_t bytes) -> uint8_t * {
-        uint8_t *p = base ? base + at : nullptr;
-        at += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
+    WsCursor c{base, 0};
     const size_t nn = n ? n : 1;
     const size_t ntiles = (nn + kScanTile - 1) / kScanTile;
-    w.perm[0] = reinterpret_cast<uint32_t *>(take(4 * nn));
-    w.perm[1] = reinterpret_cast<uint32_t *>(take(4 * nn));
-    w.keys[0] = reinterpret_cast<uint64_t *>(take(8 * nn));
-    w.keys[1] = reinterpret_cast<uint64_t *>(take(8 * nn));
-    w.flags = take(nn);
-    w.csize = reinterpret_cast<uint32_t *>(take(4 * nn));
-    w.sc = reinterpret_cast<SumPair *>(take(sizeof(SumPair) * (nn + 1)));
-    w.scan_part = reinterpret_cast<SumPair *>(take(sizeof(SumPair) * ntiles));
-    w.files = reinterpret_cast<MergeFile *>(take(sizeof(MergeFile) * (nn + 2)));
-    w.stats = reinterpret_cast<uint64_t *>(take(8 * (2 + 2 * (size_t)kMaxChunks)));
-    w.part = reinterpret_cast<uint64_t *>(take(8 * (size_t)kStatBlocks * kStatWords));
-    w.xinfo = reinterpret_cast<uint64_t *>(take(8 * nn));
-    w.abs_succ = take((size_t)kAbsMaxWin * kAbsW);
-    w.abs_bases = reinterpret_cast<uint64_t *>(take(16 * (size_t)kAbsMaxWin));
-    w.abs_head = reinterpret_cast<uint32_t *>(take(8));
+    w.perm[0] = c.take<uint32_t>(nn);
+    w.perm[1] = c.take<uint32_t>(nn);
+    w.keys[0] = c.take<uint64_t>(nn);
+    w.keys[1] = c.take<uint64_t>(nn);
+    w.flags = c.take<uint8_t>(nn);
+    w.csize = c.take<uint32_t>(nn);
+    w.sc = c.take<Sum2>(nn + 1);
+    w.scan_part = c.take<Sum2>(ntiles);
+    w.files = c.take<MergeFile>(nn + 2);
+    w.stats = c.take<uint64_t>(2 + 2 * (size_t)kMaxChunks);
+    w.part = c.take<uint64_t>((size_t)kStatBlocks * kStatWords);
+    w.xinfo = c.take<uint64_t>(nn);
+    w.abs_succ = c.take<uint8_t>((size_t)kAbsMaxWin * kAbsW);
+    w.abs_bases = c.take<uint64_t>(2 * (size_t)kAbsMaxWin);
+    w.abs_head = c.take<uint32_t>(2);
     w.sort_bytes = sort_tmp_bytes(n);
-    w.sort_tmp = take(w.sort_bytes);
-    w.total = at;
+    w.sort_tmp = c.take<uint8_t>(w.sort_bytes);
+    w.total = c.at;
     return w;
 }
 
@@ -1726,7 +1637,7 @@ extern "C" int lsm_goheap_pop_order_host(const uint32_t *rank, uint64_t n, uint3
 extern "C" uint64_t lsm_goheap_replays(const lsm_ctx *ctx) { return ctx ? ctx->goheap_replays : 0; }
 
 static_assert(sizeof(MergeFile) == 16, "MergeFile layout");
-static_assert(sizeof(SumPair) == 16, "SumPair layout");
+static_assert(sizeof(Sum2) == 16, "Sum2 layout");
 
 extern "C" size_t lsm_merge_kvs_workspace_bytes(uint64_t n) {
     if (n >= 0xFFFFFFFFull) return 0;
@@ -2075,7 +1986,7 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
                            perm, w.csize);
         hipLaunchKernelGGL(merge_scan_tiles, dim3(ntiles), dim3(kMergeThreads), 0, s, w.csize, N,
                            w.scan_part);
-        hipLaunchKernelGGL(merge_scan_partials, dim3(1), dim3(kPartThreads), 0, s, w.scan_part, ntiles,
+        hipLaunchKernelGGL(scan_partials_kernel<Sum2>, dim3(1), dim3(kPartThreads), 0, s, w.scan_part, ntiles,
                            w.sc, N);
         hipLaunchKernelGGL(goheap_rank_apply, dim3(ntiles), dim3(kMergeThreads), 0, s, w.csize, N,
                            w.scan_part, perm, rank_d);
@@ -2083,12 +1994,12 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
         // Every key distinct (N - 1 new-key flags: position 0 has rank 0 and
         // no flag): the heap pops in key order, the sorted order already is
         // its pop order -- no replay
-        SumPair *ng = static_cast<SumPair *>(ctx->host_rb);  // pinned
-        LSM_HIP_CHECK(hipMemcpyAsync(ng, w.sc + N, sizeof(SumPair), hipMemcpyDeviceToHost, s));
+        Sum2 *ng = static_cast<Sum2 *>(ctx->host_rb);  // pinned
+        LSM_HIP_CHECK(hipMemcpyAsync(ng, w.sc + N, sizeof(Sum2), hipMemcpyDeviceToHost, s));
         LSM_HIP_CHECK(hipStreamSynchronize(s));
         ctx->goheap_replays += ng->s + 1 != N;
     }
-    if (tie == LSM_TIE_GOHEAP && static_cast<SumPair *>(ctx->host_rb)->s + 1 != N) {
+    if (tie == LSM_TIE_GOHEAP && static_cast<Sum2 *>(ctx->host_rb)->s + 1 != N) {
         uint32_t *rank_d = w.perm[cur ^ 1];
         const size_t need = 8ull * N;  // ranks, then the pop order
         if (ctx->host_big_bytes < need) {
@@ -2115,7 +2026,7 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
     const uint32_t ntiles = (N + kScanTile - 1) / kScanTile;
     hipLaunchKernelGGL(merge_scan_tiles, dim3(ntiles), dim3(kMergeThreads), 0, s, w.csize, N,
                        w.scan_part);
-    hipLaunchKernelGGL(merge_scan_partials, dim3(1), dim3(kPartThreads), 0, s, w.scan_part, ntiles,
+    hipLaunchKernelGGL(scan_partials_kernel<Sum2>, dim3(1), dim3(kPartThreads), 0, s, w.scan_part, ntiles,
                        w.sc, N);
     // the walk's plateau arrays in the sort's buffers, free from here on
     uint64_t *cand_pn = w.keys[0], *cand_ext = w.keys[1];
@@ -2177,7 +2088,7 @@ extern "C" size_t lsm_gather_kvs_workspace_bytes(uint64_t nout) {
     const size_t nn = nout ? nout : 1;
     const size_t ntiles = (nn + kScanTile - 1) / kScanTile;
     return 2 * ((4 * nn + 255) & ~(size_t)255) + ((8 * nn + 255) & ~(size_t)255) +
-           sizeof(SumPair) * (ntiles + 1) + 256;
+           sizeof(Sum2) * (ntiles + 1) + 256;
 }
 
 static int gather_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_key_desc,
@@ -2193,10 +2104,10 @@ static int gather_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *
     uint32_t *kl = static_cast<uint32_t *>(d_ws);
     uint32_t *vl = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_ws) + part);
     uint64_t *ksrc = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_ws) + 2 * part);
-    SumPair *tparts = reinterpret_cast<SumPair *>(static_cast<uint8_t *>(d_ws) + 2 * part +
+    Sum2 *tparts = reinterpret_cast<Sum2 *>(static_cast<uint8_t *>(d_ws) + 2 * part +
                                                   ((8 * nn + 255) & ~(size_t)255));
     const uint32_t ntiles = (uint32_t)((nn + kScanTile - 1) / kScanTile);
-    SumPair *total = tparts + ntiles;
+    Sum2 *total = tparts + ntiles;
     const MergeIn m{d_bytes, d_key_desc, d_val_desc, N};
     if (N == 0) {  // (a device count is then 0 as well)
         LSM_HIP_CHECK(hipMemsetAsync(d_koff, 0, 8, s));
@@ -2205,7 +2116,7 @@ static int gather_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *
     }
     hipLaunchKernelGGL(gather_scan_tiles, dim3(ntiles), dim3(kMergeThreads), 0, s, m, d_idx, N, d_nout,
                        kl, vl, tparts, ksrc);
-    hipLaunchKernelGGL(merge_scan_partials, dim3(1), dim3(kPartThreads), 0, s, tparts, ntiles, total, 0);
+    hipLaunchKernelGGL(scan_partials_kernel<Sum2>, dim3(1), dim3(kPartThreads), 0, s, tparts, ntiles, total, 0);
     hipLaunchKernelGGL(gather_scan_apply, dim3(ntiles), dim3(kMergeThreads), 0, s, kl, vl, N, d_nout,
                        tparts, total, d_koff, d_voff);
     hipLaunchKernelGGL(gather_copy_kernel, dim3((N + kMergeThreads - 1) / kMergeThreads),

@@ -1,5 +1,5 @@
 """GPU parity of the straight-line DESC path for blocks that fit the LDS ring
-(decode_block_lin in go-lsm_amd/csrc/decode.hip) and of its hand-over to the
+(decode_block_lin in go-lsm_amd/csrc/decode_core.h) and of its hand-over to the
 general chase: every case against pyoracle.decode_block (descriptors, nrec,
 status, idx_value), with the descriptor buffers pre-filled with a sentinel so
 that a store past a block's verified records shows.
