@@ -11,19 +11,14 @@
 // passes join them over ping-pong buffers of (16 key bytes, slot), and
 // the finish keeps the last element of each run of equal keys, applies
 // IMemTable.RangeScan's cut and compacts the survivors' slots across logs.
-// The order is total -- (key, slot) -- so no pass needs to be stable.
-#include "common.h"
+// The order is total -- (key, slot) -- so no pass needs to be stable.  The
+// sort itself is mtsort.h's, shared with write.hip.
+#include "mtsort.h"
 
 namespace {
 
 using namespace lsm;
 
-constexpr uint32_t kTile = 1024;     // records per LDS tile (LSM_MEMTABLE_TILE)
-constexpr uint32_t kThreads = 256;   // every other kernel's workgroup
-// the tile sort's workgroup: one compare-exchange per thread and stage (its 55
-// barrier-separated stages are latency, not throughput)
-constexpr uint32_t kSortThreads = kTile / 2;
-constexpr uint32_t kPad = 0xFFFFFFFFu;  // slot of a tile's padding element
 constexpr uint32_t kTombBit = 0x80000000u;
 constexpr uint64_t kOverflowBit = 1ull << 63;
 
@@ -37,6 +32,10 @@ struct Logs {
     uint32_t nlog;
     uint32_t nslot;
     uint32_t maxrec;
+    // mtsort.h's key source: the records of log w, a slot's key
+    __device__ __forceinline__ uint32_t span(uint32_t w, uint32_t *base) const;
+    __device__ __forceinline__ Key16 key16(uint32_t slot) const;
+    __device__ __forceinline__ int cmp_tail(uint32_t a, uint32_t b) const;
 };
 
 // The records of log w this call orders: [*base, *base + n) of desc.  A log
@@ -49,29 +48,6 @@ __device__ __forceinline__ uint32_t log_span(const Logs &L, uint32_t w, uint32_t
     if (overflow) *overflow = over;
     *base = (uint32_t)b;
     return failed || over ? 0 : n;
-}
-
-__device__ __forceinline__ uint64_t load8(const uint8_t *p) {
-    uint64_t v;
-    __builtin_memcpy(&v, p, 8);
-    return v;
-}
-
-// A key's first 16 bytes as two big-endian integers, zero padded: compared as
-// (hi, lo) they order keys that differ there; equal, with either key at most
-// 16 bytes long, the shorter key is a prefix of the other and sorts first.
-struct alignas(16) Key16 {
-    uint64_t hi, lo;
-};
-
-// 8 key bytes from `at` as a big-endian integer, zero padded past the key.
-// Reads 8 bytes whatever the key's length (the input slack covers them).
-__device__ __forceinline__ uint64_t key_word(const uint8_t *key, uint32_t klen, uint32_t at) {
-    if (klen <= at) return 0;
-    uint64_t v = __builtin_bswap64(load8(key + at));
-    const uint32_t left = klen - at;
-    if (left < 8) v &= ~0ull << (8 * (8 - left));
-    return v;
 }
 
 __device__ __forceinline__ Key16 key16_of(const Logs &L, uint32_t slot) {
@@ -95,15 +71,11 @@ __device__ int key_cmp_tail(const Logs &L, uint32_t a, uint32_t b) {
     return la == lb ? 0 : (la < lb ? -1 : 1);
 }
 
-// (key, slot) order; a padding element sorts last.
-__device__ __forceinline__ bool item_less(const Logs &L, Key16 ka, uint32_t a, Key16 kb, uint32_t b) {
-    if (a == kPad) return false;
-    if (b == kPad) return true;
-    if (ka.hi != kb.hi) return ka.hi < kb.hi;
-    if (ka.lo != kb.lo) return ka.lo < kb.lo;
-    const int c = key_cmp_tail(L, a, b);
-    return c ? c < 0 : a < b;
+__device__ __forceinline__ uint32_t Logs::span(uint32_t w, uint32_t *base) const {
+    return log_span(*this, w, base, nullptr);
 }
+__device__ __forceinline__ Key16 Logs::key16(uint32_t slot) const { return key16_of(*this, slot); }
+__device__ __forceinline__ int Logs::cmp_tail(uint32_t a, uint32_t b) const { return key_cmp_tail(*this, a, b); }
 
 // kv.DeletedValue (kv/kv.go:29-31), 13 bytes; IsDeleted compares the whole value.
 __device__ bool is_tombstone_rec(const uint8_t *bytes, const lsm_rec_desc d) {
@@ -116,98 +88,6 @@ __device__ bool is_tombstone_rec(const uint8_t *bytes, const lsm_rec_desc d) {
 }
 
 __device__ bool is_tombstone(const Logs &L, uint32_t slot) { return is_tombstone_rec(L.bytes, L.desc[slot]); }
-
-// ---- tile sort: one workgroup per tile of one log --------------------------
-
-__global__ __launch_bounds__(kSortThreads) void mt_tile_sort(Logs L, Key16 *key_out, uint32_t *pos_out) {
-    __shared__ uint64_t s_hi[kTile], s_lo[kTile];
-    __shared__ uint32_t s_pos[kTile];
-    const uint32_t w = blockIdx.y;
-    uint32_t base;
-    const uint32_t n = log_span(L, w, &base, nullptr);
-    const uint32_t t0 = blockIdx.x * kTile;
-    if (t0 >= n) return;
-    const uint32_t cnt = n - t0 < kTile ? n - t0 : kTile;
-    for (uint32_t i = threadIdx.x; i < kTile; i += kSortThreads) {
-        if (i < cnt) {
-            const uint32_t slot = base + t0 + i;
-            const Key16 k = key16_of(L, slot);
-            s_hi[i] = k.hi;
-            s_lo[i] = k.lo;
-            s_pos[i] = slot;
-        } else {
-            s_hi[i] = s_lo[i] = ~0ull;
-            s_pos[i] = kPad;
-        }
-    }
-    __syncthreads();
-    // the smallest power of two that holds the tile's records
-    uint32_t m = 2;
-    while (m < cnt) m <<= 1;
-    for (uint32_t k = 2; k <= m; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = threadIdx.x; t < m / 2; t += kSortThreads) {
-                const uint32_t lo = 2 * t - (t & (j - 1)), hi = lo + j;
-                const bool up = (lo & k) == 0;
-                const Key16 ka{s_hi[lo], s_lo[lo]}, kb{s_hi[hi], s_lo[hi]};
-                const uint32_t a = s_pos[lo], b = s_pos[hi];
-                if (item_less(L, kb, b, ka, a) == up) {
-                    s_hi[lo] = kb.hi;
-                    s_lo[lo] = kb.lo;
-                    s_pos[lo] = b;
-                    s_hi[hi] = ka.hi;
-                    s_lo[hi] = ka.lo;
-                    s_pos[hi] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < cnt; i += kSortThreads) {  // the keys travel with the indices
-        key_out[base + t0 + i] = Key16{s_hi[i], s_lo[i]};
-        pos_out[base + t0 + i] = s_pos[i];
-    }
-}
-
-// ---- merge pass: runs of `run` elements joined in pairs --------------------
-
-// Each element finds its place by counting the partner run's smaller
-// elements (a bisection; the order is total, so the places are distinct).  A
-// run without a partner is copied.
-__global__ __launch_bounds__(kThreads) void mt_merge_pass(Logs L, uint32_t run, const Key16 *key_in,
-                                                         const uint32_t *pos_in, Key16 *key_out,
-                                                         uint32_t *pos_out) {
-    const uint32_t w = blockIdx.y;
-    uint32_t base;
-    const uint32_t n = log_span(L, w, &base, nullptr);
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const Key16 ka = key_in[base + i];
-    const uint32_t a = pos_in[base + i];
-    const uint32_t r = i / run;
-    const uint64_t other = (uint64_t)(r ^ 1) * run;  // the partner run's start
-    uint32_t cnt = 0;
-    if (other < n) {
-        const uint32_t o0 = (uint32_t)other;
-        const uint32_t olen = n - o0 < run ? n - o0 : run;
-        uint32_t lo = 0, hi = olen;
-        while (lo < hi) {  // one 16-byte gather per step; the slot only when the 16 bytes tie
-            const uint32_t mid = (lo + hi) >> 1;
-            const Key16 kb = key_in[base + o0 + mid];
-            bool less;
-            if (kb.hi != ka.hi) less = kb.hi < ka.hi;
-            else if (kb.lo != ka.lo) less = kb.lo < ka.lo;
-            else less = item_less(L, kb, pos_in[base + o0 + mid], ka, a);
-            if (less) lo = mid + 1;
-            else hi = mid;
-        }
-        cnt = lo;
-    }
-    const uint32_t pair0 = (r & ~1u) * run;  // < n
-    const uint32_t dst = base + pair0 + (i - r * run) + cnt;
-    key_out[dst] = ka;
-    pos_out[dst] = a;
-}
 
 // ---- finish -----------------------------------------------------------------
 
@@ -427,17 +307,6 @@ struct MsArgs {
     lsm_rec_desc *value;
 };
 
-// Keys (pa, la) and (pb, lb) whose first 16 bytes are equal: key_cmp_tail
-// with either key anywhere (a node against a probe key).
-__device__ int key_cmp_tail_at(const uint8_t *pa, uint32_t la, const uint8_t *pb, uint32_t lb) {
-    const uint32_t lm = la < lb ? la : lb;
-    for (uint32_t j = 16; j < lm; j += 8) {
-        const uint64_t x = key_word(pa, lm, j), y = key_word(pb, lm, j);
-        if (x != y) return x < y ? -1 : 1;
-    }
-    return la == lb ? 0 : (la < lb ? -1 : 1);
-}
-
 __global__ __launch_bounds__(kThreads) void mt_search(MsArgs a) {
     // the nodes the index vouches for: those its build wrote, within the buffer
     uint64_t nindexed = 0;
@@ -572,16 +441,7 @@ extern "C" int lsm_memtable_order(lsm_ctx *ctx, const uint8_t *d_bytes, const ls
     const Logs L{d_bytes, d_desc, d_rec_base, d_log_off, d_nrec, d_status, nlog, (uint32_t)nslot,
                  nslot ? max_log_records : 0};
     const uint32_t nblk = blocks_per_log(max_log_records);
-    const uint32_t ntile = (L.maxrec + kTile - 1) / kTile;
-    int cur = 0;
-    if (ntile) {
-        hipLaunchKernelGGL(mt_tile_sort, dim3(ntile, nlog), dim3(kSortThreads), 0, s, L, ws.key[0], ws.pos[0]);
-        for (uint64_t run = kTile; run < L.maxrec; run *= 2) {
-            hipLaunchKernelGGL(mt_merge_pass, dim3(nblk, nlog), dim3(kThreads), 0, s, L, (uint32_t)run,
-                               ws.key[cur], ws.pos[cur], ws.key[cur ^ 1], ws.pos[cur ^ 1]);
-            cur ^= 1;
-        }
-    }
+    const int cur = mt_sort_segments(L, nlog, L.maxrec, ws.key, ws.pos, s);
     uint32_t *flag = ws.pos[cur ^ 1];  // the idle index buffer: flags, then ranks
     if (nblk)
         hipLaunchKernelGGL(mt_flag, dim3(nblk, nlog), dim3(kThreads), 0, s, L, ws.key[cur], ws.pos[cur], flag,

@@ -1241,5 +1241,93 @@ std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::ve
     return out;
 }
 
+WriteResult WriteBatch(const std::vector<WriteOp> &ops, uint64_t mem_size0, uint64_t mem_max,
+                       const Bytes &current_wal) {
+    for (const WriteOp &op : ops)
+        if (op.op != LSM_OP_PUT && op.op != LSM_OP_DELETE) throw std::invalid_argument("WriteBatch: unknown op");
+    if (mem_max == 0 || mem_max > (1ull << 30)) throw std::invalid_argument("WriteBatch: mem_max out of range");
+    WriteResult out;
+    out.mem_size = mem_size0;
+    out.logs.resize(1);  // Mem, untouched
+    const size_t n = ops.size();
+    if (n == 0) return out;  // nothing to append: no device call
+    Device &d = Device::ThisThread();
+    // the current memtable's nodes (slots 0-9), when its log holds records
+    sstable::OrderedWALs r{};
+    uint64_t nnode = 0;
+    if (!current_wal.empty()) {
+        r = sstable::ReplayAndOrder(d, {current_wal}, LSM_MEMTABLE_ALL);
+        uint64_t fs[2];
+        int32_t st = 0;
+        d.D2H(fs, r.d_fsc, sizeof fs);
+        d.D2H(&st, r.d_st, 4);
+        d.Sync();
+        if (st != 0) throw std::runtime_error("WriteBatch: failed to read the current wal");
+        nnode = fs[1] - fs[0];
+    }
+    // the batch, CSR (slots 20-24)
+    std::vector<uint64_t> koff(n + 1, 0), voff(n + 1, 0);
+    for (size_t i = 0; i < n; i++) {
+        koff[i + 1] = koff[i] + ops[i].key.size();
+        voff[i + 1] = voff[i] + ops[i].value.size();
+    }
+    const size_t kbytes = koff[n], vbytes = voff[n];
+    uint8_t *hk = (uint8_t *)d.Host(20, pad16(kbytes));
+    uint8_t *hv = (uint8_t *)d.Host(21, pad16(vbytes));
+    uint8_t *hop = (uint8_t *)d.Host(22, pad16(n));
+    std::memset(hk, 0, pad16(kbytes));
+    std::memset(hv, 0, pad16(vbytes));
+    std::memset(hop, 0, pad16(n));
+    for (size_t i = 0; i < n; i++) {
+        std::memcpy(hk + koff[i], ops[i].key.data(), ops[i].key.size());
+        if (!ops[i].value.empty()) std::memcpy(hv + voff[i], ops[i].value.data(), ops[i].value.size());
+        hop[i] = (uint8_t)ops[i].op;
+    }
+    void *d_keys = d.Dev(20, pad16(kbytes));
+    void *d_vals = d.Dev(21, pad16(vbytes));
+    void *d_op = d.Dev(22, pad16(n));
+    void *d_koff = d.Dev(23, (n + 1) * 8);
+    void *d_voff = d.Dev(24, (n + 1) * 8);
+    d.H2D(d_keys, hk, pad16(kbytes));
+    d.H2D(d_vals, hv, pad16(vbytes));
+    d.H2D(d_op, hop, pad16(n));
+    d.H2D(d_koff, koff.data(), (n + 1) * 8);
+    d.H2D(d_voff, voff.data(), (n + 1) * 8);
+    // outputs (slots 25-29): the logs; log_start, wal_off, rec_base and the counts in one buffer
+    const uint32_t nlog_max = lsm_db_write_max_logs(n, kbytes, vbytes, mem_size0, mem_max);
+    if (nlog_max > 65535) throw std::invalid_argument("WriteBatch: the batch needs more than 65535 logs");
+    const uint32_t align = 16;
+    const uint64_t out_bytes = lsm_db_write_out_bytes(n, kbytes, vbytes, nlog_max, align);
+    const size_t m = (size_t)nlog_max + 1;
+    void *d_wal = d.Dev(25, pad16(out_bytes));
+    uint64_t *d_meta = (uint64_t *)d.Dev(26, (3 * m + 6) * 8);
+    void *d_len = d.Dev(27, (size_t)nlog_max * 4);
+    const size_t ws = lsm_db_write_workspace_bytes(n, nlog_max, mem_max);
+    void *d_ws = d.Dev(28, ws);
+    check(lsm_db_write(d.ctx(), (const uint8_t *)d_keys, (const uint64_t *)d_koff, (const uint8_t *)d_vals,
+                       (const uint64_t *)d_voff, (const uint8_t *)d_op, n, mem_size0, mem_max,
+                       nnode ? (const uint8_t *)r.d_wal : nullptr, nnode ? (const lsm_rec_desc *)r.d_desc : nullptr,
+                       nnode ? (const uint32_t *)r.d_idx : nullptr, nnode, nlog_max, align, (uint8_t *)d_wal,
+                       d_meta, d_meta + m, (uint32_t *)d_len, nullptr, d_meta + 2 * m, nullptr, d_meta + 3 * m,
+                       d_ws, ws, d.stream()),
+          "lsm_db_write");
+    std::vector<uint64_t> meta(3 * m + 6);
+    std::vector<uint32_t> len(nlog_max);
+    d.D2H(meta.data(), d_meta, meta.size() * 8);
+    d.D2H(len.data(), d_len, len.size() * 4);
+    d.Sync();
+    const uint64_t *counts = meta.data() + 3 * m;
+    if (counts[3]) throw std::runtime_error("WriteBatch: lsm_db_write overflowed its own log bound");
+    const size_t nlog = counts[0];
+    out.logs.resize(nlog);
+    out.mem_size = counts[5];
+    for (size_t s = 0; s < nlog; s++) {
+        out.logs[s].resize(len[s]);
+        if (len[s]) d.D2H(out.logs[s].data(), (const uint8_t *)d_wal + meta[m + s], len[s]);
+    }
+    d.Sync();
+    return out;
+}
+
 }  // namespace database
 }  // namespace golsm

@@ -327,5 +327,32 @@ struct GetResult {
 std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
                                    const uint32_t *level_start, const std::vector<kv::Key> &keys,
                                    int mode = LSM_DBGET_TOMBSTONE_HIDES);
+// database.Put / database.Delete (database/database.go:42-59) of a batch over
+// lsm_db_write: memtable.Manager.Insert / Delete (memtable/manager.go:40-106)
+// applied in order -- CanInsert against sizeInBytes (memtable.go:112-121),
+// promoteLocked when the pair does not fit, MemTable.Delete's (key, nil) record
+// when the current memtable holds the key (memtable.go:84-96), wal.Append of
+// KeyValuePair.EncodeTo (wal.go:85-92, kv.go:46-74).  mem_size0 is Mem's
+// sizeInBytes on entry, current_wal its log so far (its skiplist is recovered
+// from it, lsm_wal_replay -> lsm_memtable_order; empty = an empty skiplist).
+// logs[0] is what the batch appends to Mem's log (empty when op 0 already
+// rotates), logs[s > 0] the log of each memtable the batch opens: every log
+// but the last belongs to a memtable promoteLocked froze, the last to the new
+// Mem, whose sizeInBytes is mem_size.  A Delete's value is ignored.  Evicting
+// the 11th frozen memtable (sstable::BuildSSTablesFromWALs), WAL file ids and
+// I/O stay with the caller.  No ops: no device call.  Throws
+// std::invalid_argument for an unknown op or mem_max outside [1, 1 << 30].
+constexpr uint64_t kMaxMemTableSize = 2 * 1024 * 1024;  // maxMemoryTableSize
+struct WriteOp {
+    int op = LSM_OP_PUT;  // a lsm_write_op
+    kv::Key key;
+    kv::Value value;
+};
+struct WriteResult {
+    std::vector<Bytes> logs;
+    uint64_t mem_size = 0;
+};
+WriteResult WriteBatch(const std::vector<WriteOp> &ops, uint64_t mem_size0 = 0,
+                       uint64_t mem_max = kMaxMemTableSize, const Bytes &current_wal = {});
 }  // namespace database
 }  // namespace golsm

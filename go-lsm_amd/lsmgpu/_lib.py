@@ -123,6 +123,21 @@ SIGNATURES = {
                                   ctypes.c_void_p, ctypes.c_void_p, c_u32p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "lsm_db_write_max_logs": (ctypes.c_uint32, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                ctypes.c_uint64, ctypes.c_uint64]),
+    "lsm_db_write_out_bytes": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.c_uint32, ctypes.c_uint32]),
+    "lsm_db_write_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64]),
+    "lsm_db_write": (ctypes.c_int, [ctypes.c_void_p,
+                                    # the batch
+                                    c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, ctypes.c_uint64,
+                                    ctypes.c_uint64, ctypes.c_uint64,
+                                    # the current memtable's nodes
+                                    c_u8p, ctypes.c_void_p, c_u32p, ctypes.c_uint64,
+                                    ctypes.c_uint32, ctypes.c_uint32,
+                                    # outputs
+                                    c_u8p, c_u64p, c_u64p, c_u32p, ctypes.c_void_p, c_u64p, c_u32p, c_u64p,
+                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "lsm_decode_sst_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32]),
     "lsm_decode_sst": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u64p, c_u64p, ctypes.c_uint32,
                                       c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -1385,3 +1385,99 @@ def memtable_flush(ctx: Context, d_wal: torch.Tensor, wal_off: torch.Tensor, wal
                             val_bytes=nbytes, m=m, k=k, stream=stream)
     build_sst_views_into(ctx, batch, sb, d_wal, r.desc, None, mo.idx, stream=stream)
     return MemtableFlush(sb.out, sb.file_off, sb.file_size, logs, status, over, mo, r)
+
+
+# ---- database.Put / Delete (lsm_db_write) ----------------------------------------
+
+OP_PUT, OP_DELETE = 0, 1        # enum lsm_write_op
+MAX_MEMTABLE_SIZE = 2 << 20     # maxMemoryTableSize (memtable/memtable.go)
+
+
+@dataclass
+class DbWriteResult:
+    """lsm_db_write's counts and per-log arrays on the host."""
+    nlog: int
+    nrec: int
+    nbytes: int
+    overflow: bool
+    most_records: int
+    mem_size: int           # sizeInBytes of the last log: the next call's mem_size0
+    log_start: np.ndarray   # int64[nlog + 1], op index
+    wal_off: np.ndarray     # int64[nlog + 1]
+    wal_len: np.ndarray     # int64[nlog]
+    rec_base: np.ndarray    # int64[nlog + 1]
+
+
+class DbWrite:
+    """lsm_db_write's device buffers: log s is wal[wal_off[s]:wal_off[s] +
+    wal_len[s]].  log_start, wal_off, rec_base (nlog_max + 1 each) and the six
+    counts share one device tensor, so one copy reads them back."""
+
+    def __init__(self, ctx: Context, n: int, key_bytes: int, val_bytes: int, mem_size0: int, mem_max: int,
+                 nlog_max: Optional[int] = None, align: int = 16, desc: bool = True, main_slot: bool = True,
+                 fill: int = 0):
+        dev = ctx.torch_device
+        if nlog_max is None:
+            nlog_max = int(ctx.lib.lsm_db_write_max_logs(n, key_bytes, val_bytes, mem_size0, mem_max))
+        self.n, self.mem_size0, self.mem_max, self.nlog_max, self.align = n, mem_size0, mem_max, nlog_max, align
+        self.out_bytes = int(ctx.lib.lsm_db_write_out_bytes(n, key_bytes, val_bytes, nlog_max, align))
+        self.wal = torch.full((pad16(self.out_bytes),), fill, dtype=torch.uint8, device=dev)
+        m = nlog_max + 1
+        self.meta = torch.zeros(3 * m + 6, dtype=torch.int64, device=dev)
+        self.log_start, self.wal_off, self.rec_base = self.meta[:m], self.meta[m:2 * m], self.meta[2 * m:3 * m]
+        self.counts = self.meta[3 * m:]
+        self.wal_len = torch.zeros(max(nlog_max, 1), dtype=torch.int32, device=dev)
+        self.desc = torch.zeros((max(2 * n, 1), 4), dtype=torch.int32, device=dev) if desc else None
+        self.main_slot = torch.zeros(max(n, 1), dtype=torch.int32, device=dev) if main_slot else None
+        nws = int(ctx.lib.lsm_db_write_workspace_bytes(n, nlog_max, mem_max))
+        self.workspace = torch.empty(max(nws, 16), dtype=torch.uint8, device=dev)
+
+    def result(self) -> DbWriteResult:
+        """Reads the counts and the per-log arrays back."""
+        m = self.nlog_max + 1
+        h = self.meta.cpu().numpy()
+        c = h[3 * m:]
+        nlog = int(c[0])
+        return DbWriteResult(nlog, int(c[1]), int(c[2]), bool(c[3]), int(c[4]), int(c[5]),
+                             h[:nlog + 1].copy(), h[m:m + nlog + 1].copy(),
+                             self.wal_len[:nlog].cpu().numpy().view(np.uint32).astype(np.int64),
+                             h[2 * m:2 * m + nlog + 1].copy())
+
+    def replay(self, nlog: int):
+        """(DecodeResult, wal_off) as lsm_wal_replay would leave them for the
+        first nlog logs (rec_base placement, every status 0): what
+        memtable_order, memtable_search and db_get take.  No read-back."""
+        nrec = (self.rec_base[1:nlog + 1] - self.rec_base[:nlog]).to(torch.int32)
+        status = torch.zeros(max(nlog, 1), dtype=torch.int32, device=self.wal.device)
+        return DecodeResult(self.desc, nrec, status, self.rec_base[:nlog + 1]), self.wal_off[:nlog]
+
+
+def db_write_into(ctx: Context, batch: "RecordBatch", ops: torch.Tensor, w: DbWrite, cur=None,
+                  stream=None) -> None:
+    """lsm_db_write into preallocated buffers.  cur = (d_bytes, d_desc, d_idx):
+    the current memtable's nodes, d_idx being memtable_order(MEMTABLE_ALL)'s
+    idx slice of that one log over d_bytes / d_desc; None = an empty skiplist."""
+    cb, cd, ci = cur if cur is not None else (None, None, None)
+    _lib.check(ctx.lib.lsm_db_write(
+        ctx.handle, _ptr(batch.keys), _ptr(batch.koff), _ptr(batch.vals), _ptr(batch.voff), _ptr(ops),
+        batch.n, w.mem_size0, w.mem_max, _ptr(cb), _ptr(cd), _ptr(ci), int(ci.numel()) if ci is not None else 0,
+        w.nlog_max, w.align, _ptr(w.wal), _ptr(w.log_start), _ptr(w.wal_off), _ptr(w.wal_len), _ptr(w.desc),
+        _ptr(w.rec_base), _ptr(w.main_slot), _ptr(w.counts), _ptr(w.workspace), w.workspace.numel(),
+        _stream_handle(stream)), "lsm_db_write")
+
+
+def db_write(ctx: Context, batch: "RecordBatch", ops, mem_size0: int = 0, mem_max: int = MAX_MEMTABLE_SIZE,
+             cur=None, nlog_max: Optional[int] = None, align: int = 16, desc: bool = True,
+             main_slot: bool = True, fill: int = 0, stream=None) -> DbWrite:
+    """database.Put / database.Delete (database/database.go:42-59) of a batch:
+    ops[i] = OP_PUT / OP_DELETE for record i of `batch` (a Delete's value is
+    ignored).  Returns the device buffers; .result() reads the counts back,
+    .replay(nlog) hands the logs to memtable_order / memtable_search / db_get
+    without a replay."""
+    if not isinstance(ops, torch.Tensor):
+        ops = torch.from_numpy(_writable(np.asarray(ops, dtype=np.uint8))).to(ctx.torch_device)
+    w = DbWrite(ctx, batch.n, int(batch.koff_host[-1]), int(batch.voff_host[-1]), mem_size0, mem_max,
+                nlog_max=nlog_max, align=align, desc=desc, main_slot=main_slot, fill=fill)
+    if batch.n:
+        db_write_into(ctx, batch, ops, w, cur=cur, stream=stream)
+    return w

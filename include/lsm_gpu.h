@@ -659,6 +659,72 @@ int lsm_db_get(lsm_ctx *ctx,
                int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value, int32_t *d_src,
                void *d_workspace, size_t ws_bytes, void *stream);
 
+/* database.Put / database.Delete (database/database.go:42-59) of a batch of n
+ * operations in one asynchronous call: the write-ahead logs go-lsm would
+ * append, byte for byte, with memtable rotation, and the descriptors
+ * lsm_wal_replay would return for them ("The write side").
+ * The batch is CSR with the input-slack contract: op i has key
+ * d_keys[d_koff[i] .. d_koff[i+1]), value d_vals[d_voff[i] .. d_voff[i+1]) and
+ * kind d_op[i] (0 = Put, anything else = Delete; a Delete's value range is
+ * ignored).  Ops apply in order to the current memtable, whose sizeInBytes
+ * (memtable.go:112-121) is mem_size0 on entry; est(pair) = 16 + len(key) +
+ * len(value) (kv.go:118-121); mem_max is maxMemoryTableSize.
+ *   Put (manager.go:40-59): when size + est > mem_max the memtable is promoted
+ *     and an empty one takes over; then the pair is appended and size += est.
+ *   Delete (manager.go:76-106): when the memtable current BEFORE any promotion
+ *     holds the key, (key, nil) -- klen | key | vlen = 0 -- is appended to its
+ *     log, size unchanged (memtable.go:84-96); then (key, kv.DeletedValue) is
+ *     put like any pair (est = 16 + len(key) + 13).
+ * Log 0 is the memtable current on entry (it holds no op when op 0 does not
+ * fit); every further log holds its first op however large.  A key is in a
+ * memtable exactly when its log holds a record of the key, or, for log 0,
+ * when it is one of the nodes passed in: d_cur_idx[0 .. cur_nnode) =
+ * lsm_memtable_order(LSM_MEMTABLE_ALL)'s d_idx slice of that one log (slots in
+ * key order) over d_cur_bytes / d_cur_desc; NULL or cur_nnode == 0 = empty.
+ * Outputs, for s < nlog = d_counts[0]:
+ *   log s = d_wal[d_wal_off[s] .. + d_wal_len[s]); d_wal_off[s + 1] =
+ *     d_wal_off[s] + roundup(d_wal_len[s], align), so every log starts at a
+ *     multiple of align and the bytes between logs are untouched;
+ *   d_log_start[s] = the first op of log s (d_log_start[nlog] = n);
+ *   d_rec_base[s] = the records of the logs before s (d_rec_base[nlog] = all);
+ *   d_desc (optional, 2n entries): record r of log s at slot d_rec_base[s] + r,
+ *     rec_off relative to d_wal -- lsm_wal_replay's rec_base placement, which
+ *     lsm_memtable_order, lsm_memtable_search and lsm_db_get take as they are
+ *     (nrec[s] = d_rec_base[s + 1] - d_rec_base[s], status 0);
+ *   d_main_slot[i] (optional): the slot of op i's Put / tombstone record (a
+ *     Delete's (key, nil) record, when it has one, is the slot before);
+ *   d_counts = {nlog, records, bytes = d_wal_off[nlog], overflow, most records
+ *     in one log, sizeInBytes of log nlog - 1 after the batch (the next call's
+ *     mem_size0)}.
+ * Logs s < nlog - 1 are promoted memtables; evicting and flushing the 11th
+ * (promoteLocked), file ids and I/O stay with the caller.
+ * nlog_max < the logs the rule needs: d_counts = {0, 0, 0, 1, 0, 0} and no
+ * other output is promised (as lsm_segment_files).  lsm_db_write_max_logs
+ * always suffices; lsm_db_write_out_bytes bounds d_counts[2] from host-known
+ * sums (key_bytes = d_koff[n], val_bytes = d_voff[n]).  nlog_max and mem_max
+ * also size the presence launches (nlog_max logs of up to mem_max / 16 ops):
+ * pass the bound, not 65535.
+ * Checks, in this order, before any launch: ctx == NULL -> LSM_EINVAL; n == 0
+ * -> 0, nothing written; LSM_EINVAL for a NULL d_keys, d_koff, d_vals, d_voff,
+ * d_op, d_wal, d_log_start, d_wal_off, d_wal_len, d_rec_base or d_counts,
+ * mem_max == 0 or > 1 << 30, align == 0, n >= 2^31, nlog_max == 0 or > 65535,
+ * d_cur_idx != NULL with a NULL d_cur_bytes or d_cur_desc;
+ * then LSM_ESPACE for a NULL or short workspace.  No host synchronisation, no
+ * read-back, no device allocation (capturable); no pointer is kept. */
+enum lsm_write_op { LSM_OP_PUT = 0, LSM_OP_DELETE = 1 };
+uint32_t lsm_db_write_max_logs(uint64_t n, uint64_t key_bytes, uint64_t val_bytes, uint64_t mem_size0,
+                               uint64_t mem_max);
+uint64_t lsm_db_write_out_bytes(uint64_t n, uint64_t key_bytes, uint64_t val_bytes, uint32_t nlog_max,
+                                uint32_t align);
+size_t lsm_db_write_workspace_bytes(uint64_t n, uint32_t nlog_max, uint64_t mem_max);
+int lsm_db_write(lsm_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_koff, const uint8_t *d_vals,
+                 const uint64_t *d_voff, const uint8_t *d_op, uint64_t n, uint64_t mem_size0,
+                 uint64_t mem_max, const uint8_t *d_cur_bytes, const lsm_rec_desc *d_cur_desc,
+                 const uint32_t *d_cur_idx, uint64_t cur_nnode, uint32_t nlog_max, uint32_t align,
+                 uint8_t *d_wal, uint64_t *d_log_start, uint64_t *d_wal_off, uint32_t *d_wal_len,
+                 lsm_rec_desc *d_desc, uint64_t *d_rec_base, uint32_t *d_main_slot, uint64_t *d_counts,
+                 void *d_workspace, size_t ws_bytes, void *stream);
+
 /* The Seek tree of a level for lsm_level_get, built once when the level is
  * loaded (the Manager keeps each table's decoded IndexBlock in memory,
  * manager.go:226-275; Seek bisects it, index.go:157-181).  Go's bisection
