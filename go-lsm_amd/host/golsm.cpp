@@ -1071,6 +1071,134 @@ std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int sca
     return out;
 }
 
+// A tree on the device (slots 20-28): the images in one buffer, decoded, and
+// the sparse index over them -- what lsm_search, lsm_db_get and lsm_tree_scan
+// take.  h_img is the host copy the value views are read from.
+struct DeviceTree {
+    uint8_t *h_img = nullptr;
+    void *d_img = nullptr, *d_off = nullptr, *d_len = nullptr, *d_meta = nullptr, *d_idesc = nullptr,
+         *d_ival = nullptr, *d_index = nullptr;
+};
+
+static DeviceTree UploadTree(Device &d, const std::vector<Bytes> &images) {
+    DeviceTree t;
+    const size_t nfile = images.size();
+    if (!nfile) return t;
+    std::vector<uint64_t> off(nfile), len(nfile);
+    size_t total = 0;
+    for (size_t f = 0; f < nfile; f++) {
+        off[f] = total;
+        len[f] = images[f].size();
+        total += (images[f].size() + 15) & ~(size_t)15;
+    }
+    t.h_img = (uint8_t *)d.Host(2, pad16(total));
+    std::memset(t.h_img, 0, pad16(total));
+    for (size_t f = 0; f < nfile; f++) std::memcpy(t.h_img + off[f], images[f].data(), images[f].size());
+    const size_t cap = total / 4 + 1;
+    t.d_img = d.Dev(20, pad16(total));
+    t.d_off = d.Dev(21, nfile * 8);
+    t.d_len = d.Dev(22, nfile * 8);
+    t.d_meta = d.Dev(23, nfile * sizeof(lsm_sst_meta));
+    t.d_idesc = d.Dev(24, cap * sizeof(lsm_rec_desc));
+    t.d_ival = d.Dev(25, cap * 8);
+    void *d_ddesc = d.Dev(26, cap * sizeof(lsm_rec_desc));
+    const size_t dws = lsm_decode_sst_workspace_bytes((uint32_t)nfile);
+    void *d_dws = d.Dev(27, dws);
+    d.H2D(t.d_img, t.h_img, pad16(total));
+    d.H2D(t.d_off, off.data(), nfile * 8);
+    d.H2D(t.d_len, len.data(), nfile * 8);
+    check(lsm_decode_sst(d.ctx(), (const uint8_t *)t.d_img, (const uint64_t *)t.d_off, (const uint64_t *)t.d_len,
+                         (uint32_t)nfile, nullptr, (lsm_sst_meta *)t.d_meta, (lsm_rec_desc *)t.d_idesc,
+                         (int64_t *)t.d_ival, (lsm_rec_desc *)d_ddesc, d_dws, dws, d.stream()),
+          "lsm_decode_sst");
+    t.d_index = d.Dev(28, lsm_level_index_bytes((uint32_t)nfile));
+    check(lsm_level_index_build(d.ctx(), (const uint8_t *)t.d_img, (const uint64_t *)t.d_off,
+                                (const lsm_sst_meta *)t.d_meta, (uint32_t)nfile, t.d_index, d.stream()),
+          "lsm_level_index_build");
+    d.Sync();  // off / len are read by the copies queued above
+    return t;
+}
+
+std::vector<ScanResult> ScanImages(const std::vector<Bytes> &images, const uint32_t *level_start,
+                                   const std::vector<ScanRange> &ranges, uint32_t limit, int mode) {
+    if (mode != LSM_SCAN_RAW && mode != LSM_SCAN_LIVE) throw std::invalid_argument("ScanImages: unknown mode");
+    if (limit == 0) throw std::invalid_argument("ScanImages: limit is 0");
+    if (!level_start || level_start[LSM_SEARCH_LEVELS] != images.size())
+        throw std::invalid_argument("ScanImages: level_start does not end at the number of images");
+    const size_t nq = ranges.size();
+    if ((uint64_t)nq * limit >= (1ull << 32)) throw std::invalid_argument("ScanImages: too many entries");
+    std::vector<ScanResult> out(nq);
+    // no range, or no table: nothing in any range; no device call
+    if (nq == 0 || images.empty()) return out;
+    Device &d = Device::ThisThread();
+    const DeviceTree t = UploadTree(d, images);
+    // the ranges (slots 10-14) and the outputs (15, 30-35)
+    std::vector<uint64_t> lo_off(nq + 1, 0), hi_off(nq + 1, 0);
+    for (size_t q = 0; q < nq; q++) {
+        lo_off[q + 1] = lo_off[q] + ranges[q].lo.size();
+        hi_off[q + 1] = hi_off[q] + ranges[q].hi.size();
+    }
+    uint8_t *h_lo = (uint8_t *)d.Host(1, pad16(lo_off[nq]));
+    uint8_t *h_hi = (uint8_t *)d.Host(3, pad16(hi_off[nq]));
+    uint8_t *h_flags = (uint8_t *)d.Host(4, pad16(nq));
+    std::memset(h_lo, 0, pad16(lo_off[nq]));
+    std::memset(h_hi, 0, pad16(hi_off[nq]));
+    std::memset(h_flags, 0, pad16(nq));
+    for (size_t q = 0; q < nq; q++) {
+        std::memcpy(h_lo + lo_off[q], ranges[q].lo.data(), ranges[q].lo.size());
+        std::memcpy(h_hi + hi_off[q], ranges[q].hi.data(), ranges[q].hi.size());
+        h_flags[q] = ranges[q].no_upper ? LSM_SCAN_NO_UPPER : 0;
+    }
+    const size_t n = nq * (size_t)limit;
+    void *d_lo = d.Dev(10, pad16(lo_off[nq])), *d_lo_off = d.Dev(11, (nq + 1) * 8);
+    void *d_hi = d.Dev(12, pad16(hi_off[nq])), *d_hi_off = d.Dev(13, (nq + 1) * 8);
+    void *d_flags = d.Dev(14, pad16(nq));
+    void *d_count = d.Dev(15, nq * 4), *d_more = d.Dev(30, pad16(nq));
+    void *d_key = d.Dev(31, n * sizeof(lsm_rec_desc)), *d_value = d.Dev(32, n * sizeof(lsm_rec_desc));
+    void *d_table = d.Dev(33, n * 4), *d_result = d.Dev(34, n * 4);
+    const size_t ws = lsm_tree_scan_workspace_bytes(level_start, nq);
+    void *d_ws = d.Dev(35, ws ? ws : 16);
+    d.H2D(d_lo, h_lo, pad16(lo_off[nq]));
+    d.H2D(d_lo_off, lo_off.data(), (nq + 1) * 8);
+    d.H2D(d_hi, h_hi, pad16(hi_off[nq]));
+    d.H2D(d_hi_off, hi_off.data(), (nq + 1) * 8);
+    d.H2D(d_flags, h_flags, pad16(nq));
+    // no Seek tree: the Seek walks each table's decoded index (the same answers)
+    check(lsm_tree_scan(d.ctx(), (const uint8_t *)t.d_img, t.d_index, level_start, (const uint64_t *)t.d_off,
+                        (const uint64_t *)t.d_len, (const lsm_sst_meta *)t.d_meta, nullptr,
+                        (const lsm_rec_desc *)t.d_idesc, (const int64_t *)t.d_ival, nullptr, 0, 0,
+                        (const uint8_t *)d_lo, (const uint64_t *)d_lo_off, (const uint8_t *)d_hi,
+                        (const uint64_t *)d_hi_off, (const uint8_t *)d_flags, nq, limit, mode,
+                        (uint32_t *)d_count, (uint8_t *)d_more, (lsm_rec_desc *)d_key, (lsm_rec_desc *)d_value,
+                        (int32_t *)d_table, (int32_t *)d_result, d_ws, ws, d.stream()),
+          "lsm_tree_scan");
+    std::vector<uint32_t> count(nq);
+    std::vector<uint8_t> more(nq);
+    std::vector<lsm_rec_desc> key(n), value(n);
+    std::vector<int32_t> table(n), result(n);
+    d.D2H(count.data(), d_count, nq * 4);
+    d.D2H(more.data(), d_more, nq);
+    d.D2H(key.data(), d_key, n * sizeof(lsm_rec_desc));
+    d.D2H(value.data(), d_value, n * sizeof(lsm_rec_desc));
+    d.D2H(table.data(), d_table, n * 4);
+    d.D2H(result.data(), d_result, n * 4);
+    d.Sync();
+    for (size_t q = 0; q < nq; q++) {
+        out[q].more = more[q] != 0;
+        out[q].entries.resize(count[q]);
+        for (uint32_t j = 0; j < count[q]; j++) {
+            const size_t o = q * (size_t)limit + j;
+            ScanEntry &e = out[q].entries[j];
+            e.key.assign((const char *)t.h_img + key[o].rec_off + 4, key[o].key_len);
+            e.table = table[o];
+            e.result = result[o];
+            if (result[o] == LSM_GET_FOUND)
+                e.value.assign(t.h_img + value[o].rec_off + 4, t.h_img + value[o].rec_off + 4 + value[o].val_len);
+        }
+    }
+    return out;
+}
+
 }  // namespace sstable
 
 namespace memtables {
@@ -1136,7 +1264,7 @@ std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::ve
     // no memtable and no table: every Get is (nil, nil); no device call
     if (keys.empty() || (wals.empty() && images.empty())) return out;
     Device &d = Device::ThisThread();
-    const size_t nkeys = keys.size(), nlog = wals.size(), nfile = images.size();
+    const size_t nkeys = keys.size(), nlog = wals.size();
     // the memtables (slots 0-9 and 16), when there are logs
     sstable::OrderedWALs r{};
     void *d_mem_index = nullptr;
@@ -1151,42 +1279,10 @@ std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::ve
               "lsm_memtable_search_index_build");
     }
     // the tree (slots 20-28): the images in one buffer, decoded, and the sparse index over them
-    std::vector<uint64_t> off(nfile), len(nfile);
-    uint8_t *h_img = nullptr;
-    void *d_img = nullptr, *d_off = nullptr, *d_len = nullptr, *d_meta = nullptr, *d_idesc = nullptr,
-         *d_ival = nullptr, *d_index = nullptr;
-    if (nfile) {
-        size_t total = 0;
-        for (size_t f = 0; f < nfile; f++) {
-            off[f] = total;
-            len[f] = images[f].size();
-            total += (images[f].size() + 15) & ~(size_t)15;
-        }
-        h_img = (uint8_t *)d.Host(2, pad16(total));
-        std::memset(h_img, 0, pad16(total));
-        for (size_t f = 0; f < nfile; f++) std::memcpy(h_img + off[f], images[f].data(), images[f].size());
-        const size_t cap = total / 4 + 1;
-        d_img = d.Dev(20, pad16(total));
-        d_off = d.Dev(21, nfile * 8);
-        d_len = d.Dev(22, nfile * 8);
-        d_meta = d.Dev(23, nfile * sizeof(lsm_sst_meta));
-        d_idesc = d.Dev(24, cap * sizeof(lsm_rec_desc));
-        d_ival = d.Dev(25, cap * 8);
-        void *d_ddesc = d.Dev(26, cap * sizeof(lsm_rec_desc));
-        const size_t dws = lsm_decode_sst_workspace_bytes((uint32_t)nfile);
-        void *d_dws = d.Dev(27, dws);
-        d.H2D(d_img, h_img, pad16(total));
-        d.H2D(d_off, off.data(), nfile * 8);
-        d.H2D(d_len, len.data(), nfile * 8);
-        check(lsm_decode_sst(d.ctx(), (const uint8_t *)d_img, (const uint64_t *)d_off, (const uint64_t *)d_len,
-                             (uint32_t)nfile, nullptr, (lsm_sst_meta *)d_meta, (lsm_rec_desc *)d_idesc,
-                             (int64_t *)d_ival, (lsm_rec_desc *)d_ddesc, d_dws, dws, d.stream()),
-              "lsm_decode_sst");
-        d_index = d.Dev(28, lsm_level_index_bytes((uint32_t)nfile));
-        check(lsm_level_index_build(d.ctx(), (const uint8_t *)d_img, (const uint64_t *)d_off,
-                                    (const lsm_sst_meta *)d_meta, (uint32_t)nfile, d_index, d.stream()),
-              "lsm_level_index_build");
-    }
+    const sstable::DeviceTree t = sstable::UploadTree(d, images);
+    uint8_t *h_img = t.h_img;
+    void *d_img = t.d_img, *d_off = t.d_off, *d_len = t.d_len, *d_meta = t.d_meta, *d_idesc = t.d_idesc,
+         *d_ival = t.d_ival, *d_index = t.d_index;
     // the keys (slots 10-11) and the outputs (12-15, 30-33)
     std::vector<uint64_t> koff(nkeys + 1, 0);
     for (size_t i = 0; i < nkeys; i++) koff[i + 1] = koff[i] + keys[i].size();

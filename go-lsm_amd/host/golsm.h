@@ -280,6 +280,37 @@ std::vector<SSTable> CompactAndMergeKVs(const std::vector<kv::KeyValuePair> &kvs
 std::vector<Bytes> BuildSSTablesFromWALs(const std::vector<Bytes> &wals, int scan,
                                          std::vector<int32_t> *status = nullptr,
                                          uint64_t m = bloom::kDefaultM, uint64_t k = bloom::kDefaultK);
+// Range scans over a whole tree in one call (lsm_tree_scan): what a
+// database.Iterator over the SSTables delivers -- sstable.Iterator
+// (sstable/iterator.go:9-73) per table, merged in Manager.Search's order.
+// `images` are the tree's tables in lsm_search's order (level 0 newest first,
+// each deeper level by MinKey), level_start (LSM_SEARCH_LEVELS + 1 entries)
+// ending at images.size().  Per range [lo, hi) (no_upper: hi ignored) up to
+// `limit` entries in key order, each key once with the entry of the table
+// Search answers it from: its key, the answering table, result (LSM_GET_FOUND,
+// or Search's error code with an empty value) and the value's bytes.  mode is a
+// lsm_scan_mode: LSM_SCAN_LIVE leaves out keys whose answering value is the
+// tombstone, LSM_SCAN_RAW returns it as a value.  more: the walk stopped at
+// limit with a further entry to deliver.  No ranges or no images: no device
+// call.  Throws std::invalid_argument for an unknown mode, limit == 0 or a
+// level_start that does not end at images.size().
+struct ScanRange {
+    kv::Key lo, hi;
+    bool no_upper = false;
+};
+struct ScanEntry {
+    kv::Key key;
+    kv::Value value;
+    int32_t table = -1;
+    int32_t result = LSM_GET_ABSENT;
+};
+struct ScanResult {
+    std::vector<ScanEntry> entries;
+    bool more = false;
+};
+std::vector<ScanResult> ScanImages(const std::vector<Bytes> &images, const uint32_t *level_start,
+                                   const std::vector<ScanRange> &ranges, uint32_t limit,
+                                   int mode = LSM_SCAN_LIVE);
 
 }  // namespace sstable
 

@@ -15,6 +15,7 @@ from .codec import (  # noqa: F401
     level_may_contain_into, level_may_contain_workspace, level_index, level_get, level_get_into,
     level_get_tree, SeekTree, level0_get, level0_get_into, level_search_get, level_search_get_into,
     SEARCH_LEVELS, search, search_into, search_workspace,
+    SCAN_RAW, SCAN_LIVE, SCAN_NO_UPPER, tree_scan, tree_scan_into, tree_scan_workspace,
     GET_ABSENT, GET_FOUND, GET_SEEK_FAILED, GET_VALUE_LENGTH, GET_VALUE_TOO_LONG, GET_VALUE_SHORT, Merge, alloc_merge, merge_kvs, merge_kvs_into, gather_kvs,
     prepare_sst_device, sst_pairs, sst_pairs_into, compact_merge_into, TOMBSTONE, build_sst_views_into,
     TIE_INPUT, TIE_GOHEAP, goheap_pop_order,

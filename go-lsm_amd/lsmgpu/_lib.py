@@ -182,6 +182,14 @@ SIGNATURES = {
                                   c_u64p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p,
                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                   ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "lsm_tree_scan_workspace_bytes": (ctypes.c_size_t, [c_u32p, ctypes.c_uint64]),
+    "lsm_tree_scan": (ctypes.c_int, [ctypes.c_void_p, c_u8p, ctypes.c_void_p, c_u32p, c_u64p, c_u64p,
+                                     ctypes.c_void_p, c_u64p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
+                                     c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, ctypes.c_uint64, ctypes.c_uint32,
+                                     ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.c_size_t, ctypes.c_void_p]),
     "lsm_level_get_tree_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
     "lsm_level_get_tree_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u64p, ctypes.c_void_p,
                                                 ctypes.c_uint32, c_u64p, ctypes.c_void_p,

@@ -681,6 +681,73 @@ def search(ctx: Context, d_img: torch.Tensor, r: SstDecode, level_start, batch: 
     return level[:batch.n], table[:batch.n], result[:batch.n], value[:batch.n]
 
 
+SCAN_RAW, SCAN_LIVE = 0, 1  # enum lsm_scan_mode
+SCAN_NO_UPPER = 1           # LSM_SCAN_NO_UPPER, bit 0 of a range's flags
+
+
+def tree_scan_workspace(ctx: Context, level_start, nq: int) -> torch.Tensor:
+    ls = _level_start(level_start)
+    n = int(ctx.lib.lsm_tree_scan_workspace_bytes(ls.ctypes.data, nq))
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=ctx.torch_device)
+
+
+def tree_scan_into(ctx: Context, d_img: torch.Tensor, r: SstDecode, level_start, ranges: "RecordBatch",
+                   flags: torch.Tensor, limit: int, mode: int, index: torch.Tensor, count: torch.Tensor,
+                   more: torch.Tensor, key: torch.Tensor, value: torch.Tensor, table: torch.Tensor,
+                   result: torch.Tensor, tree: Optional[SeekTree] = None,
+                   ws: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lsm_tree_scan: up to `limit` entries of every range over the whole tree
+    decoded into r (search_into's tree arguments), in key order, each key
+    answered by the table Manager.Search answers it from.  `ranges` is a pair
+    of CSRs in one RecordBatch: range q is [keys q, vals q) -- lo in
+    ranges.keys / koff, hi in ranges.vals / voff; flags uint8 per range
+    (SCAN_NO_UPPER: hi is ignored).  count int32[nq] (uint32 values), more
+    uint8[nq]; key / value int32[nq * limit, 4] (lsm_rec_desc), table / result
+    int32[nq * limit]: range q's entries at [q * limit, q * limit + count[q])."""
+    ls = _level_start(level_start)
+    if int(ls[-1]) != r.nfile:
+        raise ValueError(f"level_start ends at {int(ls[-1])}, the tree holds {r.nfile} tables")
+    if ws is None:
+        ws = tree_scan_workspace(ctx, ls, ranges.n)
+    nf = r.nfile
+    _lib.check(ctx.lib.lsm_tree_scan(
+        ctx.handle, _ptr(d_img) if nf else None, _ptr(index) if nf else None, ls.ctypes.data,
+        _ptr(r.d_file_off) if nf else None, _ptr(r.d_file_len) if nf else None, _ptr(r.meta) if nf else None,
+        None, _ptr(r.idx_desc) if nf else None, _ptr(r.idx_value) if nf else None,
+        _ptr(tree.data) if tree is not None else None, tree.max_nidx if tree is not None else 0,
+        tree.data.numel() if tree is not None else 0,
+        _ptr(ranges.keys), _ptr(ranges.koff), _ptr(ranges.vals), _ptr(ranges.voff), _ptr(flags), ranges.n,
+        limit, mode, _ptr(count), _ptr(more), _ptr(key), _ptr(value), _ptr(table), _ptr(result),
+        _ptr(ws), ws.numel(), _stream_handle(stream)), "lsm_tree_scan")
+
+
+def tree_scan(ctx: Context, d_img: torch.Tensor, r: SstDecode, level_start, ranges: "RecordBatch",
+              flags, limit: int, mode: int = SCAN_LIVE, index: Optional[torch.Tensor] = None,
+              tree: Optional[SeekTree] = None, stream=None):
+    """-> (count int32[nq], more uint8[nq], key int32[nq * limit, 4], value
+    int32[nq * limit, 4], table int32[nq * limit], result int32[nq * limit])
+    on the device.  flags: a uint8 device tensor, or host values to upload."""
+    dev = ctx.torch_device
+    nq = ranges.n
+    n = max(nq * max(limit, 0), 1)
+    count = torch.empty(max(nq, 1), dtype=torch.int32, device=dev)
+    more = torch.empty(max(nq, 1), dtype=torch.uint8, device=dev)
+    key = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    value = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    table = torch.empty(n, dtype=torch.int32, device=dev)
+    result = torch.empty(n, dtype=torch.int32, device=dev)
+    if not isinstance(flags, torch.Tensor):
+        f = np.zeros(max(nq, 1), np.uint8)
+        f[:nq] = np.asarray(flags, dtype=np.uint8)
+        flags = torch.from_numpy(f).to(dev)
+    if index is None:
+        index = level_index(ctx, d_img, r, stream=stream)
+    if nq:
+        tree_scan_into(ctx, d_img, r, level_start, ranges, flags, limit, mode, index, count, more, key,
+                       value, table, result, tree=tree, stream=stream)
+    return count[:nq], more[:nq], key[:nq * limit], value[:nq * limit], table[:nq * limit], result[:nq * limit]
+
+
 # ---- encode -----------------------------------------------------------------
 
 @dataclass

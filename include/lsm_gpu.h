@@ -56,7 +56,8 @@ extern "C" {
  * lsm_memtable_order_workspace_bytes (a memtable's contents from its WAL);
  * lsm_memtable_search with lsm_memtable_search_index_bytes / _index_build
  * (memtable.Manager.Search over those memtables) and lsm_db_get with
- * lsm_db_get_workspace_bytes (database.Get in one call). */
+ * lsm_db_get_workspace_bytes (database.Get in one call); lsm_tree_scan and
+ * lsm_tree_scan_workspace_bytes (batched range scan over a whole tree). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -611,6 +612,94 @@ int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
                int32_t *d_level, int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value,
                const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
                void *d_workspace, size_t ws_bytes, void *stream);
+
+/* Batched range scan over a whole tree in one asynchronous call (added within
+ * ABI 7): the ordered read go-lsm's iterators add up to -- sstable.Iterator
+ * (sstable/iterator.go:9-73) over block.Iterator.Seek / Next / Valid / Key /
+ * ValueOffset (sstable/block/index.go:157-181), the shape database.Iterator
+ * (database/iterator.go) declares.  The tree is lsm_search's, argument for
+ * argument.  For each of nq ranges [lo, hi) in Go string order (CSR: lo of
+ * range q is d_lo[d_lo_off[q] .. d_lo_off[q + 1]), hi likewise; input-slack
+ * contract; d_flags[q] & LSM_SCAN_NO_UPPER: no upper bound, hi is ignored) it
+ * returns up to `limit` entries in ascending key order, each key once,
+ * answered by the table Manager.Search (manager.go:99-133) answers it from:
+ * the scan of a range is Search applied to every key the tree holds in it.
+ *   Which tables take part: table t with d_meta[t].stage == LSM_SST_OK and
+ *     nidx > 0; its entries are the nidx index entries the decode kept, in
+ *     index order.  A level-0 table is one source; level 0's sources come in
+ *     the tree's order (newest first), then the levels in order.  The tables
+ *     of a level >= 1 that take part form one source, walked one after the
+ *     other in sparse-index order.
+ *   The Seek: a table is entered by Iterator.Seek(lo), Go's bisection for the
+ *     first entry with key >= lo (index.go:157-181) -- the bisection
+ *     lsm_level_get runs, through the Seek tree or over the index, so d_tree
+ *     == NULL and a tree give identical output (a tree buffer below
+ *     lsm_level_get_tree_bytes(nfile, tree_nidx): LSM_ESPACE).  In a level
+ *     >= 1 the table entered is the one the sparse index picks (manager.go:
+ *     186-192); a Seek that runs off its end goes on at entry 0 of the next
+ *     table.
+ *   Which source answers: the first source, in the order above, that holds
+ *     the key -- Search's order.  The filters are not consulted: the Builder
+ *     added every key of a table's index to its filter.  Deviation: with a
+ *     corrupted filter lsm_search can miss a key that the scan returns.
+ *   The boundary key: within a level >= 1 a key can be both the last key of
+ *     table f and the first of table f + 1 (the merge forgets the last written
+ *     key at every flush, merge.go:57-85, so compaction outputs do this).  The
+ *     entry of f + 1 answers, once: f + 1 is the table the sparse index picks
+ *     for the key, so it is what Search returns, though it is the older pair.
+ *   Preconditions: every participating table's index is strictly ascending;
+ *     the tables of a level >= 1 are in MinKey order with ranges that meet at
+ *     most in one boundary key.  Outside them the output is unspecified, but
+ *     every access stays inside the caller's buffers and every walk ends.
+ *   Emission: entry j of range q is at q * limit + j.  d_key = the answering
+ *     index entry's descriptor as d_idx_desc holds it {rec_off into d_img,
+ *     key_len, val_len = 8}; d_table = the answering table's position in the
+ *     tree's list; d_result / d_value exactly lsm_level_get's for that entry
+ *     (GetValueByOffset, sstable.go:271-296): LSM_GET_FOUND with the value's
+ *     view, or an error code with a zero view -- an entry whose value read
+ *     fails is emitted with its code, as Search returns that error for the
+ *     key.  d_key / d_value are what lsm_gather_kvs takes as d_key_desc /
+ *     d_val_desc.
+ *   Modes: LSM_SCAN_RAW -- a value of exactly the 13 tombstone bytes (kv.go:
+ *     29-31) is an ordinary value, as for Search.  LSM_SCAN_LIVE -- a key whose
+ *     answering entry is LSM_GET_FOUND with exactly those bytes is not emitted
+ *     and does not count towards limit.  In both the tombstone hides the key
+ *     in every later source.
+ *   Counts: d_count[q] <= limit entries were emitted; d_more[q] = 1 exactly
+ *     when the walk stopped at limit and a further key of the range would
+ *     have been emitted in this mode (LIVE: a tail of tombstones gives 0).
+ *     Slots j >= d_count[q] are unspecified.  An empty range (lo >= hi) and an
+ *     empty tree give count 0, more 0.
+ * Checks, in this order, before any launch: ctx == NULL -> LSM_EINVAL; nq == 0
+ * -> 0, nothing written; LSM_EINVAL for a level_start that does not start at 0
+ * or decreases, limit == 0, nq * limit >= 2^32, an unknown mode, a NULL d_lo /
+ * d_lo_off / d_hi / d_hi_off / d_flags or output pointer, a non-empty tree
+ * with a NULL tree input other than d_rec_base / d_tree; LSM_ESPACE for the
+ * tree buffer or the workspace.  Workspace: lsm_tree_scan_workspace_bytes =
+ * 32 bytes per range and source (a source per level-0 table and one per level
+ * 1..6), 0 for an empty tree or a level_start that does not start at 0 or
+ * decreases.  Two launches on the stream: the Seeks, one thread per range and
+ * source, leave each source's first entry in the workspace; the walk runs a
+ * wave per range with a lane per source, any level-0 width (past 64 sources
+ * the lanes' cursors stay in the workspace).  No host synchronisation, no
+ * read-back, no device allocation, no pointer kept. */
+enum lsm_scan_mode { LSM_SCAN_RAW = 0, LSM_SCAN_LIVE = 1 };
+#define LSM_SCAN_NO_UPPER 1u /* bit 0 of d_flags[q]: the range has no upper bound, hi is ignored */
+size_t lsm_tree_scan_workspace_bytes(const uint32_t *level_start, uint64_t nq);
+int lsm_tree_scan(lsm_ctx *ctx,
+                  /* the tree: exactly lsm_search's inputs, with the same meaning */
+                  const uint8_t *d_img, const void *d_index,
+                  const uint32_t *level_start, /* HOST, LSM_SEARCH_LEVELS + 1 entries */
+                  const uint64_t *d_file_off, const uint64_t *d_file_len, const lsm_sst_meta *d_meta,
+                  const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value,
+                  const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
+                  /* the ranges: [lo, hi) in Go string order, CSR, input-slack contract */
+                  const uint8_t *d_lo, const uint64_t *d_lo_off, const uint8_t *d_hi,
+                  const uint64_t *d_hi_off, const uint8_t *d_flags, uint64_t nq, uint32_t limit, int mode,
+                  /* outputs: range q's entries at [q * limit, q * limit + d_count[q]) */
+                  uint32_t *d_count, uint8_t *d_more, lsm_rec_desc *d_key, lsm_rec_desc *d_value,
+                  int32_t *d_table, int32_t *d_result,
+                  void *d_workspace, size_t ws_bytes, void *stream);
 
 /* database.Get (database/database.go:24-40) of nkeys keys in one asynchronous
  * call: lsm_memtable_search over the memtables (its arguments, d_mem_index /
