@@ -87,10 +87,13 @@ __device__ __forceinline__ uint64_t table_base(const GetArgs &a, uint32_t t) {
     return a.rec_base ? a.rec_base[t] : a.file_off[t] / 4;
 }
 
-// The entries of table t that take part: nidx of a table that decoded, else 0.
+// The entries of table t that take part: nidx of a table SSTable.DecodeFrom
+// loads (sstable.go:101-125 reads header, filter, footer and index; the data
+// block is compaction's, so its damage -- stages 5 and 6 -- keeps the table in
+// the Manager, and Search answers from it), else 0.
 __device__ __forceinline__ uint32_t table_entries(const GetArgs &a, uint32_t t) {
     const lsm_sst_meta &M = a.meta[t];
-    return M.stage == LSM_SST_OK ? M.nidx : 0;
+    return M.stage == LSM_SST_OK || M.stage == LSM_SST_DATA || M.stage == LSM_SST_MISMATCH ? M.nidx : 0;
 }
 
 // The next table of [t + 1, end) that takes part, or kTsNone.

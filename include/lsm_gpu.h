@@ -624,9 +624,15 @@ int lsm_search(lsm_ctx *ctx, const uint8_t *d_img, const void *d_index,
  * returns up to `limit` entries in ascending key order, each key once,
  * answered by the table Manager.Search (manager.go:99-133) answers it from:
  * the scan of a range is Search applied to every key the tree holds in it.
- *   Which tables take part: table t with d_meta[t].stage == LSM_SST_OK and
- *     nidx > 0; its entries are the nidx index entries the decode kept, in
- *     index order.  A level-0 table is one source; level 0's sources come in
+ *   Which tables take part: table t that Go would have loaded and that has
+ *     entries -- d_meta[t].stage is LSM_SST_OK, LSM_SST_DATA or
+ *     LSM_SST_MISMATCH, and nidx > 0.  SSTable.DecodeFrom (sstable.go:101-125)
+ *     reads header, filter, footer and index; the data block is read only for
+ *     compaction, so a table with a damaged data block is in the Manager,
+ *     Search and lsm_search answer from it, and so does the scan.  Stages 1-4
+ *     are DecodeFrom's failures: such a table is in no Manager and stays out.
+ *     A table's entries are the nidx index entries the decode kept, in index
+ *     order.  A level-0 table is one source; level 0's sources come in
  *     the tree's order (newest first), then the levels in order.  The tables
  *     of a level >= 1 that take part form one source, walked one after the
  *     other in sparse-index order.

@@ -47,11 +47,12 @@ def to_ranges(ctx, ranges):
     return batch, flags
 
 
-def check(ctx, dt, ranges, limit, mode, batch=None):
-    """lsm_tree_scan with and without the Seek tree against the reference."""
+def check(ctx, dt, ranges, limit, mode, batch=None, want=None):
+    """lsm_tree_scan with and without the Seek tree against the reference
+    (want: its scan_batch answer for these ranges, where the caller has it)."""
     ref = dt.host.ref
     assert ref.absent == 0
-    wc, wm, widx = ref.scan_batch(ranges, limit, mode)
+    wc, wm, widx = want if want is not None else ref.scan_batch(ranges, limit, mode)
     if batch is None:
         batch = to_ranges(ctx, ranges)
     sel = widx >= 0
@@ -149,6 +150,78 @@ def test_value_errors(ctx):
     assert ref.voff[3] == 0 and ref.vlen[3] == 0 and ref.voff[7] == 0 and ref.vlen[7] == 0
 
 
+def test_width_16(ctx):
+    """16 sources: the first row's four shifts are the whole minimum."""
+    case = cases.width_16()
+    assert int(case.tree.level_start[1]) + cases.LEVELS - 1 == 16
+    _, emitted = run_case(ctx, case)
+    assert emitted > 300
+
+
+def test_width_17(ctx):
+    """17 sources: the full 64-lane minimum, level 6 in lane 16."""
+    case = cases.width_17()
+    assert int(case.tree.level_start[1]) + cases.LEVELS - 1 == 17
+    _, emitted = run_case(ctx, case)
+    assert emitted > 300
+
+
+def test_width_64(ctx):
+    """64 sources: every lane of the register path holds a head; a key per
+    16-lane row that one source of the row holds alone."""
+    case = cases.width_64()
+    assert int(case.tree.level_start[1]) + cases.LEVELS - 1 == 64
+    _, emitted = run_case(ctx, case)
+    assert emitted > 300
+    ref = case.tree.ref
+    idx, _ = ref.scan(b"row", b"rox", False, 64, RAW)
+    assert [int(ref.table[i]) for i in idx] == list(cases.ROW_TABLES)
+
+
+def test_width_65(ctx):
+    """65 sources: the workspace path, level 6 alone in the second round; the
+    patched value offsets are emitted with their codes."""
+    case = cases.width_65()
+    assert int(case.tree.level_start[1]) + cases.LEVELS - 1 == 65
+    _, emitted = run_case(ctx, case)
+    assert emitted > 300
+    ref = case.tree.ref
+    assert ref.res[ref.keys.index(b"verr-neg")] == ora.GET_SEEK_FAILED
+    assert ref.res[ref.keys.index(b"verr-end")] == ora.GET_VALUE_LENGTH
+
+
+def test_wide_3rounds(ctx):
+    """129 sources: three rounds, one live lane in the last."""
+    case = cases.wide_3rounds()
+    assert int(case.tree.level_start[1]) + cases.LEVELS - 1 == 129
+    _, emitted = run_case(ctx, case)
+    assert emitted > 30
+
+
+def test_damaged(ctx):
+    """Tables with a damaged data block (stages 5 and 6) take part, as in
+    lsm_search; tables whose index did not decode (stage 4) do not."""
+    case = cases.damaged()
+    dt, emitted = run_case(ctx, case)
+    assert [(int(m["stage"]), int(m["nidx"])) for m in dt.r.meta_numpy()] == cases.DAMAGED_TABLES
+    assert emitted > 150
+    ref = case.tree.ref
+    assert (ref.table[[ref.keys.index(k) for k in (b"d11", b"d12", b"d05", b"d60")]] == [0, 5, 8, 9]).all()
+
+
+def test_strides(ctx):
+    """Both grid-stride loops iterate: the walk's waves take three ranges each
+    (the last pass ragged), the Seeks pass 16,384 x 256 (range, source) pairs.
+    A pattern of distinct ranges -- full, partial, empty, lo >= hi -- tiled to
+    nq; the reference is the pattern's, tiled."""
+    for tiled in (cases.strides_walk(), cases.strides_seek()):
+        dt = device_tree(ctx, tiled.tree)
+        batch = to_ranges(ctx, tiled.ranges)
+        for mode in (RAW, LIVE):
+            wc, _, _ = check(ctx, dt, tiled.ranges, tiled.limit, mode, batch, want=tiled.want(mode))
+            assert wc.size == tiled.nq and wc[-1] == wc[(tiled.nq - 1) % len(tiled.pattern)]
+
+
 def test_many_ranges(ctx):
     case = cases.many_ranges()
     dt = device_tree(ctx, case.tree)
@@ -160,7 +233,8 @@ def test_many_ranges(ctx):
 
 def test_edges(ctx):
     """An empty tree; nq == 0 leaves the outputs untouched; LSM_ESPACE for a
-    short tree buffer; LSM_EINVAL for limit == 0 and for a bad mode."""
+    short tree buffer and for a workspace one byte short; LSM_EINVAL for
+    limit == 0, a bad mode, nq * limit == 2^32 and a decreasing level_start."""
     case = cases.empty_tree()
     dt = device_tree(ctx, case.tree)
     batch, flags = to_ranges(ctx, case.ranges)
@@ -195,5 +269,19 @@ def test_edges(ctx):
         lsmgpu.tree_scan_into(ctx, dt.d_img, dt.r, case.tree.level_start, batch, flags, 0, LIVE, dt.index, *out)
     with pytest.raises(RuntimeError, match="code -1"):
         lsmgpu.tree_scan_into(ctx, dt.d_img, dt.r, case.tree.level_start, batch, flags, 4, 2, dt.index, *out)
+    ws = lsmgpu.tree_scan_workspace(ctx, case.tree.level_start, nq)
+    assert ws.numel() == nq * (int(case.tree.level_start[1]) + cases.LEVELS - 1) * 32
+    with pytest.raises(RuntimeError, match="code -4"):
+        lsmgpu.tree_scan_into(ctx, dt.d_img, dt.r, case.tree.level_start, batch, flags, 4, LIVE, dt.index, *out,
+                              ws=ws[:ws.numel() - 1])
+    # nq * limit == 2^32: refused before anything is read, so the batch's claimed size is never used
+    with pytest.raises(RuntimeError, match="code -1"):
+        lsmgpu.tree_scan_into(ctx, dt.d_img, dt.r, case.tree.level_start, dataclasses.replace(batch, n=1 << 16),
+                              flags, 1 << 16, LIVE, dt.index, *out, ws=ws)
+    down = np.array(case.tree.level_start).copy()
+    down[3] = down[2] - 1                       # level 2 ends before it starts; the list's end is unchanged
+    assert down[-1] == dt.r.nfile
+    with pytest.raises(RuntimeError, match="code -1"):
+        lsmgpu.tree_scan_into(ctx, dt.d_img, dt.r, down, batch, flags, 4, LIVE, dt.index, *out, ws=ws)
     torch.cuda.synchronize()
     assert all(bool((x == 77).all()) for x in out)

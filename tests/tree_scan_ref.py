@@ -1,7 +1,7 @@
 """The reference answer of lsm_tree_scan: the scan of a range is Manager.Search
 applied to every key the tree holds in that range.  The distinct keys of every
-participating table's index entries (ora.sst_decode; stage 0 and nidx > 0)
-are sorted bytewise and answered once by search_ref.search -- what
+participating table's index entries (ora.sst_decode; takes_part: a stage Go's
+DecodeFrom loads -- 0, 5 or 6 -- and nidx > 0) are sorted bytewise and answered once by search_ref.search -- what
 tests/test_search_ref.py pins against the Go text -- then a range keeps the
 keys in [lo, hi), applies the mode and the limit.
 tests/test_tree_scan_ref.py pins this against a restatement of the iterator
@@ -17,6 +17,14 @@ from search_ref import csr
 
 RAW, LIVE = 0, 1
 TOMBSTONE = "～DELETED～".encode()  # kv.DeletedValue, kv/kv.go:29-31
+LOADED_STAGES = (0, 5, 6)   # SSTable.DecodeFrom (sstable.go:101-125) does not read the data block
+
+
+def takes_part(meta):
+    """A table Go would have loaded (stages 1-4 are DecodeFrom's failures; 5
+    and 6 are damage to the data block, which only compaction reads) that has
+    entries: what Manager.Search and sstable.Iterator see."""
+    return meta.stage in LOADED_STAGES and meta.nidx > 0
 
 
 class TreeRef:
@@ -32,7 +40,7 @@ class TreeRef:
         for t, d in enumerate(dec):
             meta, idesc = d[1], d[2]
             e = {}
-            if meta.stage == 0 and meta.nidx > 0:
+            if takes_part(meta):
                 o = int(offs[t])
                 for x in idesc:
                     at, kl = o + int(x["rec_off"]), int(x["key_len"])
