@@ -1337,6 +1337,124 @@ std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::ve
     return out;
 }
 
+std::vector<ScanResult> ScanFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
+                                     const uint32_t *level_start, const std::vector<sstable::ScanRange> &ranges,
+                                     uint32_t limit, int mode) {
+    if (mode != LSM_SCAN_RAW && mode != LSM_SCAN_LIVE) throw std::invalid_argument("ScanFromWALs: unknown mode");
+    if (limit == 0) throw std::invalid_argument("ScanFromWALs: limit is 0");
+    if (!level_start || level_start[LSM_SEARCH_LEVELS] != images.size())
+        throw std::invalid_argument("ScanFromWALs: level_start does not end at the number of images");
+    const size_t nq = ranges.size(), nlog = wals.size(), nfile = images.size();
+    if ((uint64_t)nq * limit >= (1ull << 32)) throw std::invalid_argument("ScanFromWALs: too many entries");
+    if (nlog > 65535) throw std::invalid_argument("ScanFromWALs: more than 65535 logs");
+    std::vector<ScanResult> out(nq);
+    // no range, or neither a memtable nor a table: nothing in any range; no device call
+    if (nq == 0 || (nlog == 0 && nfile == 0)) return out;
+    Device &d = Device::ThisThread();
+    // the memtables (slots 0-9 and 16), when there are logs
+    sstable::OrderedWALs r{};
+    void *d_mem_index = nullptr;
+    size_t ib = 0;
+    if (nlog) {
+        r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
+        ib = lsm_memtable_search_index_bytes(r.nslot);
+        d_mem_index = d.Dev(16, ib);
+        check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
+                                              (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)nlog, r.nslot,
+                                              d_mem_index, ib, d.stream()),
+              "lsm_memtable_search_index_build");
+    }
+    // the tree (slots 20-28) and its Seek tree (slot 29), sized for the largest table
+    const sstable::DeviceTree t = sstable::UploadTree(d, images);
+    void *d_tree = nullptr;
+    uint32_t tree_nidx = 0;
+    size_t tree_bytes = 0;
+    if (nfile) {
+        std::vector<lsm_sst_meta> meta(nfile);
+        d.D2H(meta.data(), t.d_meta, nfile * sizeof(lsm_sst_meta));
+        d.Sync();
+        for (const lsm_sst_meta &m : meta) tree_nidx = std::max(tree_nidx, m.nidx);
+        tree_bytes = lsm_level_get_tree_bytes((uint32_t)nfile, tree_nidx);
+        if (tree_bytes) {
+            d_tree = d.Dev(29, tree_bytes);
+            check(lsm_level_get_tree_build(d.ctx(), (const uint8_t *)t.d_img, (const uint64_t *)t.d_off,
+                                           (const lsm_sst_meta *)t.d_meta, (uint32_t)nfile, nullptr,
+                                           (const lsm_rec_desc *)t.d_idesc, tree_nidx, d_tree, tree_bytes,
+                                           d.stream()),
+                  "lsm_level_get_tree_build");
+        }
+    }
+    // the ranges (slots 10-14) and the outputs (15, 30-36)
+    std::vector<uint64_t> lo_off(nq + 1, 0), hi_off(nq + 1, 0);
+    for (size_t q = 0; q < nq; q++) {
+        lo_off[q + 1] = lo_off[q] + ranges[q].lo.size();
+        hi_off[q + 1] = hi_off[q] + ranges[q].hi.size();
+    }
+    uint8_t *h_lo = (uint8_t *)d.Host(1, pad16(lo_off[nq]));
+    uint8_t *h_hi = (uint8_t *)d.Host(3, pad16(hi_off[nq]));
+    uint8_t *h_flags = (uint8_t *)d.Host(4, pad16(nq));
+    std::memset(h_lo, 0, pad16(lo_off[nq]));
+    std::memset(h_hi, 0, pad16(hi_off[nq]));
+    std::memset(h_flags, 0, pad16(nq));
+    for (size_t q = 0; q < nq; q++) {
+        std::memcpy(h_lo + lo_off[q], ranges[q].lo.data(), ranges[q].lo.size());
+        std::memcpy(h_hi + hi_off[q], ranges[q].hi.data(), ranges[q].hi.size());
+        h_flags[q] = ranges[q].no_upper ? LSM_SCAN_NO_UPPER : 0;
+    }
+    const size_t n = nq * (size_t)limit;
+    void *d_lo = d.Dev(10, pad16(lo_off[nq])), *d_lo_off = d.Dev(11, (nq + 1) * 8);
+    void *d_hi = d.Dev(12, pad16(hi_off[nq])), *d_hi_off = d.Dev(13, (nq + 1) * 8);
+    void *d_flags = d.Dev(14, pad16(nq));
+    void *d_count = d.Dev(15, nq * 4), *d_more = d.Dev(30, pad16(nq));
+    void *d_key = d.Dev(31, n * sizeof(lsm_rec_desc)), *d_value = d.Dev(32, n * sizeof(lsm_rec_desc));
+    void *d_table = d.Dev(33, n * 4), *d_result = d.Dev(34, n * 4), *d_src = d.Dev(36, n * 4);
+    const size_t ws = lsm_db_scan_workspace_bytes((uint32_t)nlog, level_start, nq);
+    void *d_ws = d.Dev(35, ws ? ws : 16);
+    d.H2D(d_lo, h_lo, pad16(lo_off[nq]));
+    d.H2D(d_lo_off, lo_off.data(), (nq + 1) * 8);
+    d.H2D(d_hi, h_hi, pad16(hi_off[nq]));
+    d.H2D(d_hi_off, hi_off.data(), (nq + 1) * 8);
+    d.H2D(d_flags, h_flags, pad16(nq));
+    check(lsm_db_scan(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc, (const uint32_t *)r.d_idx,
+                      r.d_fsc, (uint32_t)nlog, d_mem_index, ib, (const uint8_t *)t.d_img, t.d_index, level_start,
+                      (const uint64_t *)t.d_off, (const uint64_t *)t.d_len, (const lsm_sst_meta *)t.d_meta, nullptr,
+                      (const lsm_rec_desc *)t.d_idesc, (const int64_t *)t.d_ival, d_tree, tree_nidx, tree_bytes,
+                      (const uint8_t *)d_lo, (const uint64_t *)d_lo_off, (const uint8_t *)d_hi,
+                      (const uint64_t *)d_hi_off, (const uint8_t *)d_flags, nq, limit, mode, (uint32_t *)d_count,
+                      (uint8_t *)d_more, (lsm_rec_desc *)d_key, (lsm_rec_desc *)d_value, (int32_t *)d_src,
+                      (int32_t *)d_table, (int32_t *)d_result, d_ws, ws, d.stream()),
+          "lsm_db_scan");
+    std::vector<uint32_t> count(nq);
+    std::vector<uint8_t> more(nq);
+    std::vector<lsm_rec_desc> key(n), value(n);
+    std::vector<int32_t> src(n), table(n), result(n);
+    d.D2H(count.data(), d_count, nq * 4);
+    d.D2H(more.data(), d_more, nq);
+    d.D2H(key.data(), d_key, n * sizeof(lsm_rec_desc));
+    d.D2H(value.data(), d_value, n * sizeof(lsm_rec_desc));
+    d.D2H(src.data(), d_src, n * 4);
+    d.D2H(table.data(), d_table, n * 4);
+    d.D2H(result.data(), d_result, n * 4);
+    d.Sync();
+    for (size_t q = 0; q < nq; q++) {
+        out[q].more = more[q] != 0;
+        out[q].entries.resize(count[q]);
+        for (uint32_t j = 0; j < count[q]; j++) {
+            const size_t o = q * (size_t)limit + j;
+            ScanEntry &e = out[q].entries[j];
+            // d_src says which buffer the views are into: the logs or the images
+            const uint8_t *base = src[o] == LSM_SRC_MEMTABLE ? r.h : t.h_img;
+            e.key.assign((const char *)base + key[o].rec_off + 4, key[o].key_len);
+            e.src = src[o];
+            e.table = table[o];
+            e.result = result[o];
+            if (result[o] == LSM_GET_FOUND)
+                e.value.assign(base + value[o].rec_off + 4, base + value[o].rec_off + 4 + value[o].val_len);
+        }
+    }
+    return out;
+}
+
 WriteResult WriteBatch(const std::vector<WriteOp> &ops, uint64_t mem_size0, uint64_t mem_max,
                        const Bytes &current_wal) {
     for (const WriteOp &op : ops)

@@ -358,6 +358,34 @@ struct GetResult {
 std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
                                    const uint32_t *level_start, const std::vector<kv::Key> &keys,
                                    int mode = LSM_DBGET_TOMBSTONE_HIDES);
+
+// The database's range scan over lsm_db_scan: sstable::ScanImages with the
+// memtables recovered from `wals` (oldest first, as GetFromWALs) in front.
+// lsm_wal_replay -> lsm_memtable_order (LSM_MEMTABLE_ALL) ->
+// lsm_memtable_search_index_build -> lsm_decode_sst -> lsm_level_get_tree_build
+// -> lsm_db_scan, with the memtable index and the Seek tree.  Per range up to
+// `limit` entries in key order, each key once, answered by the newest memtable
+// that holds it, else by the table Search answers it from: src is
+// LSM_SRC_MEMTABLE (table = the log, result = LSM_GET_FOUND, value the node's
+// bytes -- the 13 tombstone bytes in LSM_SCAN_RAW) or LSM_SRC_SSTABLE (as
+// ScanImages).  mode is a lsm_scan_mode: LSM_SCAN_LIVE leaves out a key whose
+// answering entry is a tombstone, which hides it in every older source in both
+// modes.  No ranges, or neither logs nor images: no device call.  Throws
+// std::invalid_argument as ScanImages does.
+struct ScanEntry {
+    kv::Key key;
+    kv::Value value;
+    int32_t src = LSM_SRC_NONE;
+    int32_t table = -1;
+    int32_t result = LSM_GET_ABSENT;
+};
+struct ScanResult {
+    std::vector<ScanEntry> entries;
+    bool more = false;
+};
+std::vector<ScanResult> ScanFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
+                                     const uint32_t *level_start, const std::vector<sstable::ScanRange> &ranges,
+                                     uint32_t limit, int mode = LSM_SCAN_LIVE);
 // database.Put / database.Delete (database/database.go:42-59) of a batch over
 // lsm_db_write: memtable.Manager.Insert / Delete (memtable/manager.go:40-106)
 // applied in order -- CanInsert against sizeInBytes (memtable.go:112-121),

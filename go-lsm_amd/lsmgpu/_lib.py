@@ -190,6 +190,22 @@ SIGNATURES = {
                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.c_size_t, ctypes.c_void_p]),
+    "lsm_db_scan_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint32, c_u32p, ctypes.c_uint64]),
+    "lsm_db_scan": (ctypes.c_int, [ctypes.c_void_p,
+                                   # the memtables
+                                   c_u8p, ctypes.c_void_p, c_u32p, c_u64p, ctypes.c_uint32,
+                                   ctypes.c_void_p, ctypes.c_size_t,
+                                   # the tree
+                                   c_u8p, ctypes.c_void_p, c_u32p, c_u64p, c_u64p, ctypes.c_void_p,
+                                   c_u64p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_uint32, ctypes.c_size_t,
+                                   # the ranges, the limit and the mode
+                                   c_u8p, c_u64p, c_u8p, c_u64p, c_u8p, ctypes.c_uint64, ctypes.c_uint32,
+                                   ctypes.c_int,
+                                   # outputs
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "lsm_level_get_tree_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
     "lsm_level_get_tree_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u64p, ctypes.c_void_p,
                                                 ctypes.c_uint32, c_u64p, ctypes.c_void_p,

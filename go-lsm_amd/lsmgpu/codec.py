@@ -1397,6 +1397,85 @@ def db_get(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder
                  out.result[:n], out.value[:n], out.src[:n])
 
 
+# ---- the database scan (lsm_db_scan) ------------------------------------------
+
+@dataclass
+class DbScan:
+    """lsm_db_scan's outputs on the device: range q's entries at
+    [q * limit, q * limit + count[q])."""
+    count: torch.Tensor   # int32[nq] (uint32 values)
+    more: torch.Tensor    # uint8[nq]
+    key: torch.Tensor     # int32[nq * limit, 4]: lsm_rec_desc into d_wal (memtable) or d_img (table)
+    value: torch.Tensor   # int32[nq * limit, 4]: the value's view, in the same buffer
+    src: torch.Tensor     # int32[nq * limit]: SRC_MEMTABLE or SRC_SSTABLE
+    table: torch.Tensor   # int32[nq * limit]: the log, or the table's index in the tree
+    result: torch.Tensor  # int32[nq * limit]: GET_*
+
+
+def db_scan_workspace(ctx: Context, nlog: int, level_start, nq: int) -> torch.Tensor:
+    ls = _level_start(level_start)
+    n = int(ctx.lib.lsm_db_scan_workspace_bytes(nlog, ls.ctypes.data, nq))
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=ctx.torch_device)
+
+
+def db_scan_into(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder,
+                 d_img: torch.Tensor, sd: SstDecode, level_start, ranges: "RecordBatch",
+                 flags: torch.Tensor, limit: int, mode: int, index: torch.Tensor, out: DbScan,
+                 mem_index: Optional[torch.Tensor] = None, tree: Optional[SeekTree] = None,
+                 ws: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lsm_db_scan: up to `limit` entries of every range over the memtables of
+    mo (db_get_into's memtable arguments; the newest log answers first) and
+    then the tree decoded into sd (tree_scan_into's tree arguments), in key
+    order, each key once.  `ranges` / flags / limit / mode as tree_scan_into.
+    index = level_index over sd; mem_index = memtable_search_index."""
+    ls = _level_start(level_start)
+    if int(ls[-1]) != sd.nfile:
+        raise ValueError(f"level_start ends at {int(ls[-1])}, the tree holds {sd.nfile} tables")
+    if ws is None:
+        ws = db_scan_workspace(ctx, mo.nlog, ls, ranges.n)
+    nf, nl = sd.nfile, mo.nlog
+    _lib.check(ctx.lib.lsm_db_scan(
+        ctx.handle, _ptr(d_wal) if nl else None, _ptr(r.desc) if nl else None, _ptr(mo.idx) if nl else None,
+        _ptr(mo.file_start) if nl else None, nl,
+        _ptr(mem_index) if mem_index is not None else None,
+        mem_index.numel() if mem_index is not None else 0,
+        _ptr(d_img) if nf else None, _ptr(index) if nf else None, ls.ctypes.data,
+        _ptr(sd.d_file_off) if nf else None, _ptr(sd.d_file_len) if nf else None,
+        _ptr(sd.meta) if nf else None, None, _ptr(sd.idx_desc) if nf else None,
+        _ptr(sd.idx_value) if nf else None,
+        _ptr(tree.data) if tree is not None else None, tree.max_nidx if tree is not None else 0,
+        tree.data.numel() if tree is not None else 0,
+        _ptr(ranges.keys), _ptr(ranges.koff), _ptr(ranges.vals), _ptr(ranges.voff), _ptr(flags), ranges.n,
+        limit, mode, _ptr(out.count), _ptr(out.more), _ptr(out.key), _ptr(out.value), _ptr(out.src),
+        _ptr(out.table), _ptr(out.result), _ptr(ws), ws.numel(), _stream_handle(stream)), "lsm_db_scan")
+
+
+def db_scan(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrder, d_img: torch.Tensor,
+            sd: SstDecode, level_start, ranges: "RecordBatch", flags, limit: int, mode: int = SCAN_LIVE,
+            index: Optional[torch.Tensor] = None, mem_index: Optional[torch.Tensor] = None,
+            tree: Optional[SeekTree] = None, stream=None) -> DbScan:
+    """-> DbScan of device tensors, cut to nq ranges and nq * limit entries.
+    flags: a uint8 device tensor, or host values to upload."""
+    dev = ctx.torch_device
+    nq = ranges.n
+    n = max(nq * max(limit, 0), 1)
+    i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
+    out = DbScan(i32(max(nq, 1)), torch.empty(max(nq, 1), dtype=torch.uint8, device=dev), i32((n, 4)),
+                 i32((n, 4)), i32(n), i32(n), i32(n))
+    if not isinstance(flags, torch.Tensor):
+        f = np.zeros(max(nq, 1), np.uint8)
+        f[:nq] = np.asarray(flags, dtype=np.uint8)
+        flags = torch.from_numpy(f).to(dev)
+    if index is None and sd.nfile:
+        index = level_index(ctx, d_img, sd, stream=stream)
+    if nq:
+        db_scan_into(ctx, d_wal, r, mo, d_img, sd, level_start, ranges, flags, limit, mode, index, out,
+                     mem_index=mem_index, tree=tree, stream=stream)
+    e = nq * limit
+    return DbScan(out.count[:nq], out.more[:nq], out.key[:e], out.value[:e], out.src[:e], out.table[:e],
+                  out.result[:e])
+
+
 @dataclass
 class MemtableFlush:
     """memtable_flush's result: image f is out[file_off[f]:file_off[f] +

@@ -57,7 +57,9 @@ extern "C" {
  * lsm_memtable_search with lsm_memtable_search_index_bytes / _index_build
  * (memtable.Manager.Search over those memtables) and lsm_db_get with
  * lsm_db_get_workspace_bytes (database.Get in one call); lsm_tree_scan and
- * lsm_tree_scan_workspace_bytes (batched range scan over a whole tree). */
+ * lsm_tree_scan_workspace_bytes (batched range scan over a whole tree);
+ * lsm_db_scan and lsm_db_scan_workspace_bytes (that scan with the memtables in
+ * front: the batched database scan). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -753,6 +755,93 @@ int lsm_db_get(lsm_ctx *ctx,
                int32_t *d_mem_result, int32_t *d_log, uint32_t *d_slot, int32_t *d_level,
                int32_t *d_table, int32_t *d_result, lsm_rec_desc *d_value, int32_t *d_src,
                void *d_workspace, size_t ws_bytes, void *stream);
+
+/* Batched range scan over the memtables and the tree in one asynchronous call
+ * (added within ABI 7): lsm_tree_scan with the memtables in front, the step
+ * that took lsm_search to lsm_db_get.  The memtables are lsm_memtable_search's
+ * inputs (logs OLDEST FIRST, d_mem_index / mem_index_bytes its d_index /
+ * index_bytes), the tree is lsm_search's, argument for argument, the ranges,
+ * limit and mode are lsm_tree_scan's.  With an empty tree it is the batched
+ * memtable range query (memtable/iterator.go leaves that as a TODO).
+ *   Sources, in answering order: the memtable of log nlog - 1 (Mem), then logs
+ *     nlog - 2 .. 0 -- memtable.Manager.Search's order (memtable/manager.go:
+ *     61-74) -- then lsm_tree_scan's sources, unchanged: each level-0 table in
+ *     the tree's order, then one source per level 1..6.  Source s < nlog is log
+ *     nlog - 1 - s.  A log with no nodes (failed, empty or overflowed:
+ *     d_file_start[w] == d_file_start[w + 1]) is a source that never has a
+ *     head.
+ *   The memtable Seek: a memtable source is entered at its first node with key
+ *     >= lo, the lower bound over d_idx[d_file_start[w] .. d_file_start[w + 1]),
+ *     and advances node by node in d_idx order.  d_idx must be the
+ *     LSM_MEMTABLE_ALL order; a LSM_MEMTABLE_RANGESCAN order is a subset and
+ *     cannot be detected (lsm_memtable_search's caveat).
+ *   Which source answers: each key is emitted once, from the first source in
+ *     that order that holds it.  As the existing calls: the scan of a range
+ *     is, for every distinct key any source holds in [lo, hi),
+ *     lsm_memtable_search's answer when that is not LSM_MEM_MISS, else
+ *     lsm_search's.
+ *   Modes (lsm_scan_mode): LSM_SCAN_RAW -- a tombstone is an ordinary value;
+ *     for a memtable node d_value is the view of its 13 bytes
+ *     (lsm_memtable_search zeroes that view, the scan does not).
+ *     LSM_SCAN_LIVE -- a key whose answering entry is a tombstone (a memtable
+ *     node with exactly kv.DeletedValue, or a table entry that is
+ *     LSM_GET_FOUND with those bytes) is not emitted and does not count
+ *     towards limit.  In both the tombstone hides the key in every later
+ *     source.  A replayed empty value (key, "") is a found value of length 0 in
+ *     both modes, as lsm_memtable_search documents.
+ *   Emission at slot o = q * limit + j: d_src[o] = LSM_SRC_MEMTABLE or
+ *     LSM_SRC_SSTABLE.  A memtable entry: d_key[o] = d_desc[slot] verbatim (the
+ *     KV descriptor into d_bytes), d_value[o] = {rec_off + 4 + key_len, 0,
+ *     val_len}, d_table[o] = the log w, d_result[o] = LSM_GET_FOUND.  A table
+ *     entry: exactly lsm_tree_scan's four outputs.  d_count / d_more as in
+ *     lsm_tree_scan (LIVE: a tail of tombstones gives more = 0); slots past
+ *     d_count[q] are unspecified.
+ *   Deviation: skiplist.Iterator skips deleted nodes in Seek and its Valid()
+ *     is false at a tombstone (skiplist/iterator.go:49-70), so a `for Valid()`
+ *     loop stops at the first tombstone -- the quirk LSM_MEMTABLE_RANGESCAN
+ *     restates for the flush.  go-lsm has no database iterator to be exact to,
+ *     so the scan offers no "exact" mode: every node takes part.
+ *   Degenerate inputs: nlog == 0 gives lsm_tree_scan's outputs with d_src =
+ *     LSM_SRC_SSTABLE; an empty tree scans the memtables alone (the tree
+ *     pointers may be NULL); with both empty d_count and d_more are zeroed by
+ *     memsets and the call returns 0.
+ * Checks, in this order, all before any launch: ctx == NULL -> LSM_EINVAL; nq
+ * == 0 -> 0, nothing written; LSM_EINVAL for a level_start that does not start
+ * at 0 or that decreases, limit == 0, nq >= 2^32 or nq * limit >= 2^32, an
+ * unknown mode, nlog > 65535, a NULL range, flag or output pointer (d_src
+ * included), nlog > 0 with a NULL d_bytes / d_desc / d_idx / d_file_start, a
+ * non-empty tree with a NULL tree input other than d_rec_base / d_tree;
+ * LSM_ESPACE for d_mem_index != NULL with mem_index_bytes below
+ * lsm_memtable_search_index_bytes(1), a tree buffer below
+ * lsm_level_get_tree_bytes(nfile, tree_nidx), a NULL or short workspace.
+ * Workspace: lsm_db_scan_workspace_bytes = 32 * nq * (nlog + level_start[1] +
+ * 6) bytes when nlog + nfile > 0 (a head per range and source); 0 when both
+ * are empty or level_start is bad; SIZE_MAX when the product leaves 64 bits.
+ * Two launches on the stream: the Seeks, one thread per range and source (a
+ * memtable thread bisects its log's nodes, through the index where the log
+ * lies inside the indexed count), then the walk, a wave per range and a lane
+ * per source, any width.  No host synchronisation, no read-back, no device
+ * allocation, no pointer kept (capturable).  d_mem_index and d_tree are
+ * optional; the output is identical with and without each. */
+size_t lsm_db_scan_workspace_bytes(uint32_t nlog, const uint32_t *level_start, uint64_t nq);
+int lsm_db_scan(lsm_ctx *ctx,
+                /* the memtables: lsm_memtable_search's inputs, logs OLDEST FIRST */
+                const uint8_t *d_bytes, const lsm_rec_desc *d_desc, const uint32_t *d_idx,
+                const uint64_t *d_file_start, uint32_t nlog, const void *d_mem_index,
+                size_t mem_index_bytes,
+                /* the tree: lsm_search's inputs, argument for argument */
+                const uint8_t *d_img, const void *d_index,
+                const uint32_t *level_start, /* HOST, LSM_SEARCH_LEVELS + 1 entries */
+                const uint64_t *d_file_off, const uint64_t *d_file_len, const lsm_sst_meta *d_meta,
+                const uint64_t *d_rec_base, const lsm_rec_desc *d_idx_desc, const int64_t *d_idx_value,
+                const void *d_tree, uint32_t tree_nidx, size_t tree_bytes,
+                /* the ranges: lsm_tree_scan's */
+                const uint8_t *d_lo, const uint64_t *d_lo_off, const uint8_t *d_hi,
+                const uint64_t *d_hi_off, const uint8_t *d_flags, uint64_t nq, uint32_t limit, int mode,
+                /* outputs: range q's entries at [q * limit, q * limit + d_count[q]) */
+                uint32_t *d_count, uint8_t *d_more, lsm_rec_desc *d_key, lsm_rec_desc *d_value,
+                int32_t *d_src, int32_t *d_table, int32_t *d_result,
+                void *d_workspace, size_t ws_bytes, void *stream);
 
 /* database.Put / database.Delete (database/database.go:42-59) of a batch of n
  * operations in one asynchronous call: the write-ahead logs go-lsm would
