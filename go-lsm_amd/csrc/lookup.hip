@@ -852,7 +852,7 @@ __global__ __launch_bounds__(256) void get_tree_build_kernel(GetArgs a, uint8_t 
 // bisection (through the Seek tree, or over the index), the exact-match
 // test, then GetValueByOffset (sstable.go:271-296).  -> a lsm_get_result;
 // the value's view in v on LSM_GET_FOUND.  The two halves are seek.h's, shared
-// with the range scan (treescan.hip).
+// with the range scans (treescan.hip).
 __device__ __forceinline__ int32_t get_in_table(const GetArgs &a, uint32_t t, const uint32_t kw[4],
                                                 uint64_t kl, const uint8_t *kp, lsm_rec_desc &v) {
     SeekTable T;

@@ -2,7 +2,7 @@
 // 16-byte big-endian key prefixes, the level's sparse-index search, and the two
 // halves of searchFromTable past MayContain -- Iterator.Seek's bisection
 // (through the Seek tree or over the index) and GetValueByOffset.  lookup.hip
-// (the Gets and Search) and treescan.hip (the range scan) run this one copy.
+// (the Gets and Search) and treescan.hip (the range scans) run this one copy.
 #pragma once
 
 #include "common.h"

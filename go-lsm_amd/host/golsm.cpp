@@ -1119,6 +1119,84 @@ static DeviceTree UploadTree(Device &d, const std::vector<Bytes> &images) {
     return t;
 }
 
+// lsm_memtable_search's index over r's nodes (slot 16); *ib = its bytes.
+static void *BuildSearchIndex(Device &d, const OrderedWALs &r, size_t *ib) {
+    *ib = lsm_memtable_search_index_bytes(r.nslot);
+    void *d_index = d.Dev(16, *ib);
+    check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
+                                          (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)r.nlog, r.nslot, d_index,
+                                          *ib, d.stream()),
+          "lsm_memtable_search_index_build");
+    return d_index;
+}
+
+// n keys as a CSR on the device: the bytes (zero padded to 16) in slot dslot
+// by way of pinned slot hslot, the offsets in slot dslot + 1.  off is the
+// offsets' host copy, which the queued upload reads.
+struct DeviceCSR {
+    void *d_bytes = nullptr, *d_off = nullptr;
+    std::vector<uint64_t> off;
+};
+
+template <class F>
+static DeviceCSR UploadCSR(Device &d, size_t n, F key, int dslot, int hslot) {
+    DeviceCSR c;
+    c.off.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) c.off[i + 1] = c.off[i] + key(i).size();
+    const size_t bytes = pad16(c.off[n]);
+    uint8_t *h = (uint8_t *)d.Host(hslot, bytes);
+    std::memset(h, 0, bytes);
+    for (size_t i = 0; i < n; i++) std::memcpy(h + c.off[i], key(i).data(), key(i).size());
+    c.d_bytes = d.Dev(dslot, bytes);
+    c.d_off = d.Dev(dslot + 1, (n + 1) * 8);
+    d.H2D(c.d_bytes, h, bytes);
+    d.H2D(c.d_off, c.off.data(), (n + 1) * 8);
+    return c;
+}
+
+// The probe keys of a Search or a Get (slots 10-11).
+static DeviceCSR UploadKeys(Device &d, const std::vector<kv::Key> &keys) {
+    return UploadCSR(d, keys.size(), [&](size_t i) -> const kv::Key & { return keys[i]; }, 10, 1);
+}
+
+// The ranges of a scan (slots 10-14) and its outputs (15, 30-34), n = nq *
+// limit entries; Read queues the outputs' copies back.
+struct DeviceScan {
+    DeviceCSR lo, hi;
+    void *d_flags, *d_count, *d_more, *d_key, *d_value, *d_table, *d_result;
+    std::vector<uint32_t> count;
+    std::vector<uint8_t> more;
+    std::vector<lsm_rec_desc> key, value;
+    std::vector<int32_t> table, result;
+
+    DeviceScan(Device &d, const std::vector<ScanRange> &ranges, size_t n)
+        : count(ranges.size()), more(ranges.size()), key(n), value(n), table(n), result(n) {
+        const size_t nq = ranges.size();
+        lo = UploadCSR(d, nq, [&](size_t q) -> const kv::Key & { return ranges[q].lo; }, 10, 1);
+        hi = UploadCSR(d, nq, [&](size_t q) -> const kv::Key & { return ranges[q].hi; }, 12, 3);
+        uint8_t *h_flags = (uint8_t *)d.Host(4, pad16(nq));
+        std::memset(h_flags, 0, pad16(nq));
+        for (size_t q = 0; q < nq; q++) h_flags[q] = ranges[q].no_upper ? LSM_SCAN_NO_UPPER : 0;
+        d_flags = d.Dev(14, pad16(nq));
+        d.H2D(d_flags, h_flags, pad16(nq));
+        d_count = d.Dev(15, nq * 4);
+        d_more = d.Dev(30, pad16(nq));
+        d_key = d.Dev(31, n * sizeof(lsm_rec_desc));
+        d_value = d.Dev(32, n * sizeof(lsm_rec_desc));
+        d_table = d.Dev(33, n * 4);
+        d_result = d.Dev(34, n * 4);
+    }
+
+    void Read(Device &d) {
+        d.D2H(count.data(), d_count, count.size() * 4);
+        d.D2H(more.data(), d_more, more.size());
+        d.D2H(key.data(), d_key, key.size() * sizeof(lsm_rec_desc));
+        d.D2H(value.data(), d_value, value.size() * sizeof(lsm_rec_desc));
+        d.D2H(table.data(), d_table, table.size() * 4);
+        d.D2H(result.data(), d_result, result.size() * 4);
+    }
+};
+
 std::vector<ScanResult> ScanImages(const std::vector<Bytes> &images, const uint32_t *level_start,
                                    const std::vector<ScanRange> &ranges, uint32_t limit, int mode) {
     if (mode != LSM_SCAN_RAW && mode != LSM_SCAN_LIVE) throw std::invalid_argument("ScanImages: unknown mode");
@@ -1132,68 +1210,35 @@ std::vector<ScanResult> ScanImages(const std::vector<Bytes> &images, const uint3
     if (nq == 0 || images.empty()) return out;
     Device &d = Device::ThisThread();
     const DeviceTree t = UploadTree(d, images);
-    // the ranges (slots 10-14) and the outputs (15, 30-35)
-    std::vector<uint64_t> lo_off(nq + 1, 0), hi_off(nq + 1, 0);
-    for (size_t q = 0; q < nq; q++) {
-        lo_off[q + 1] = lo_off[q] + ranges[q].lo.size();
-        hi_off[q + 1] = hi_off[q] + ranges[q].hi.size();
-    }
-    uint8_t *h_lo = (uint8_t *)d.Host(1, pad16(lo_off[nq]));
-    uint8_t *h_hi = (uint8_t *)d.Host(3, pad16(hi_off[nq]));
-    uint8_t *h_flags = (uint8_t *)d.Host(4, pad16(nq));
-    std::memset(h_lo, 0, pad16(lo_off[nq]));
-    std::memset(h_hi, 0, pad16(hi_off[nq]));
-    std::memset(h_flags, 0, pad16(nq));
-    for (size_t q = 0; q < nq; q++) {
-        std::memcpy(h_lo + lo_off[q], ranges[q].lo.data(), ranges[q].lo.size());
-        std::memcpy(h_hi + hi_off[q], ranges[q].hi.data(), ranges[q].hi.size());
-        h_flags[q] = ranges[q].no_upper ? LSM_SCAN_NO_UPPER : 0;
-    }
+    // the ranges (slots 10-14), the outputs (15, 30-34) and the workspace (35)
     const size_t n = nq * (size_t)limit;
-    void *d_lo = d.Dev(10, pad16(lo_off[nq])), *d_lo_off = d.Dev(11, (nq + 1) * 8);
-    void *d_hi = d.Dev(12, pad16(hi_off[nq])), *d_hi_off = d.Dev(13, (nq + 1) * 8);
-    void *d_flags = d.Dev(14, pad16(nq));
-    void *d_count = d.Dev(15, nq * 4), *d_more = d.Dev(30, pad16(nq));
-    void *d_key = d.Dev(31, n * sizeof(lsm_rec_desc)), *d_value = d.Dev(32, n * sizeof(lsm_rec_desc));
-    void *d_table = d.Dev(33, n * 4), *d_result = d.Dev(34, n * 4);
+    DeviceScan sc(d, ranges, n);
     const size_t ws = lsm_tree_scan_workspace_bytes(level_start, nq);
     void *d_ws = d.Dev(35, ws ? ws : 16);
-    d.H2D(d_lo, h_lo, pad16(lo_off[nq]));
-    d.H2D(d_lo_off, lo_off.data(), (nq + 1) * 8);
-    d.H2D(d_hi, h_hi, pad16(hi_off[nq]));
-    d.H2D(d_hi_off, hi_off.data(), (nq + 1) * 8);
-    d.H2D(d_flags, h_flags, pad16(nq));
     // no Seek tree: the Seek walks each table's decoded index (the same answers)
     check(lsm_tree_scan(d.ctx(), (const uint8_t *)t.d_img, t.d_index, level_start, (const uint64_t *)t.d_off,
                         (const uint64_t *)t.d_len, (const lsm_sst_meta *)t.d_meta, nullptr,
                         (const lsm_rec_desc *)t.d_idesc, (const int64_t *)t.d_ival, nullptr, 0, 0,
-                        (const uint8_t *)d_lo, (const uint64_t *)d_lo_off, (const uint8_t *)d_hi,
-                        (const uint64_t *)d_hi_off, (const uint8_t *)d_flags, nq, limit, mode,
-                        (uint32_t *)d_count, (uint8_t *)d_more, (lsm_rec_desc *)d_key, (lsm_rec_desc *)d_value,
-                        (int32_t *)d_table, (int32_t *)d_result, d_ws, ws, d.stream()),
+                        (const uint8_t *)sc.lo.d_bytes, (const uint64_t *)sc.lo.d_off,
+                        (const uint8_t *)sc.hi.d_bytes, (const uint64_t *)sc.hi.d_off,
+                        (const uint8_t *)sc.d_flags, nq, limit, mode, (uint32_t *)sc.d_count,
+                        (uint8_t *)sc.d_more, (lsm_rec_desc *)sc.d_key, (lsm_rec_desc *)sc.d_value,
+                        (int32_t *)sc.d_table, (int32_t *)sc.d_result, d_ws, ws, d.stream()),
           "lsm_tree_scan");
-    std::vector<uint32_t> count(nq);
-    std::vector<uint8_t> more(nq);
-    std::vector<lsm_rec_desc> key(n), value(n);
-    std::vector<int32_t> table(n), result(n);
-    d.D2H(count.data(), d_count, nq * 4);
-    d.D2H(more.data(), d_more, nq);
-    d.D2H(key.data(), d_key, n * sizeof(lsm_rec_desc));
-    d.D2H(value.data(), d_value, n * sizeof(lsm_rec_desc));
-    d.D2H(table.data(), d_table, n * 4);
-    d.D2H(result.data(), d_result, n * 4);
+    sc.Read(d);
     d.Sync();
     for (size_t q = 0; q < nq; q++) {
-        out[q].more = more[q] != 0;
-        out[q].entries.resize(count[q]);
-        for (uint32_t j = 0; j < count[q]; j++) {
+        out[q].more = sc.more[q] != 0;
+        out[q].entries.resize(sc.count[q]);
+        for (uint32_t j = 0; j < sc.count[q]; j++) {
             const size_t o = q * (size_t)limit + j;
+            const lsm_rec_desc &k = sc.key[o], &v = sc.value[o];
             ScanEntry &e = out[q].entries[j];
-            e.key.assign((const char *)t.h_img + key[o].rec_off + 4, key[o].key_len);
-            e.table = table[o];
-            e.result = result[o];
-            if (result[o] == LSM_GET_FOUND)
-                e.value.assign(t.h_img + value[o].rec_off + 4, t.h_img + value[o].rec_off + 4 + value[o].val_len);
+            e.key.assign((const char *)t.h_img + k.rec_off + 4, k.key_len);
+            e.table = sc.table[o];
+            e.result = sc.result[o];
+            if (e.result == LSM_GET_FOUND)
+                e.value.assign(t.h_img + v.rec_off + 4, t.h_img + v.rec_off + 4 + v.val_len);
         }
     }
     return out;
@@ -1209,29 +1254,16 @@ std::vector<SearchResult> SearchWALs(const std::vector<Bytes> &wals, const std::
     Device &d = Device::ThisThread();
     const sstable::OrderedWALs r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
     const size_t nkeys = keys.size();
-    std::vector<uint64_t> koff(nkeys + 1, 0);
-    for (size_t i = 0; i < nkeys; i++) koff[i + 1] = koff[i] + keys[i].size();
-    const size_t kbytes = koff[nkeys];
-    uint8_t *hk = (uint8_t *)d.Host(1, pad16(kbytes));
-    std::memset(hk, 0, pad16(kbytes));
-    for (size_t i = 0; i < nkeys; i++) std::memcpy(hk + koff[i], keys[i].data(), keys[i].size());
-    void *d_keys = d.Dev(10, pad16(kbytes));
-    void *d_koff = d.Dev(11, (nkeys + 1) * 8);
+    const sstable::DeviceCSR k = sstable::UploadKeys(d, keys);
     void *d_res = d.Dev(12, nkeys * 4);
     void *d_log = d.Dev(13, nkeys * 4);
     void *d_slot = d.Dev(14, nkeys * 4);
     void *d_val = d.Dev(15, nkeys * sizeof(lsm_rec_desc));
-    const size_t ib = lsm_memtable_search_index_bytes(r.nslot);
-    void *d_index = d.Dev(16, ib);
-    d.H2D(d_keys, hk, pad16(kbytes));
-    d.H2D(d_koff, koff.data(), (nkeys + 1) * 8);
-    check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
-                                          (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)r.nlog, r.nslot,
-                                          d_index, ib, d.stream()),
-          "lsm_memtable_search_index_build");
+    size_t ib = 0;
+    void *d_index = sstable::BuildSearchIndex(d, r, &ib);
     check(lsm_memtable_search(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
                               (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)r.nlog, d_index, ib,
-                              (const uint8_t *)d_keys, (const uint64_t *)d_koff, nkeys, (int32_t *)d_res,
+                              (const uint8_t *)k.d_bytes, (const uint64_t *)k.d_off, nkeys, (int32_t *)d_res,
                               (int32_t *)d_log, (uint32_t *)d_slot, (lsm_rec_desc *)d_val, d.stream()),
           "lsm_memtable_search");
     std::vector<int32_t> res(nkeys), log(nkeys);
@@ -1271,12 +1303,7 @@ std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::ve
     size_t ib = 0;
     if (nlog) {
         r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
-        ib = lsm_memtable_search_index_bytes(r.nslot);
-        d_mem_index = d.Dev(16, ib);
-        check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
-                                              (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)nlog, r.nslot,
-                                              d_mem_index, ib, d.stream()),
-              "lsm_memtable_search_index_build");
+        d_mem_index = sstable::BuildSearchIndex(d, r, &ib);
     }
     // the tree (slots 20-28): the images in one buffer, decoded, and the sparse index over them
     const sstable::DeviceTree t = sstable::UploadTree(d, images);
@@ -1284,29 +1311,20 @@ std::vector<GetResult> GetFromWALs(const std::vector<Bytes> &wals, const std::ve
     void *d_img = t.d_img, *d_off = t.d_off, *d_len = t.d_len, *d_meta = t.d_meta, *d_idesc = t.d_idesc,
          *d_ival = t.d_ival, *d_index = t.d_index;
     // the keys (slots 10-11) and the outputs (12-15, 30-33)
-    std::vector<uint64_t> koff(nkeys + 1, 0);
-    for (size_t i = 0; i < nkeys; i++) koff[i + 1] = koff[i] + keys[i].size();
-    const size_t kbytes = koff[nkeys];
-    uint8_t *hk = (uint8_t *)d.Host(1, pad16(kbytes));
-    std::memset(hk, 0, pad16(kbytes));
-    for (size_t i = 0; i < nkeys; i++) std::memcpy(hk + koff[i], keys[i].data(), keys[i].size());
-    void *d_keys = d.Dev(10, pad16(kbytes));
-    void *d_koff = d.Dev(11, (nkeys + 1) * 8);
+    const sstable::DeviceCSR k = sstable::UploadKeys(d, keys);
     void *d_res = d.Dev(12, nkeys * 4), *d_log = d.Dev(13, nkeys * 4), *d_slot = d.Dev(14, nkeys * 4);
     void *d_val = d.Dev(15, nkeys * sizeof(lsm_rec_desc));
     void *d_level = d.Dev(30, nkeys * 4), *d_table = d.Dev(31, nkeys * 4), *d_tres = d.Dev(32, nkeys * 4);
     void *d_src = d.Dev(33, nkeys * 4);
     const size_t ws = lsm_db_get_workspace_bytes(level_start, nkeys);
     void *d_ws = d.Dev(34, ws ? ws : 16);
-    d.H2D(d_keys, hk, pad16(kbytes));
-    d.H2D(d_koff, koff.data(), (nkeys + 1) * 8);
     // no Seek tree: the Seek walks each table's decoded index (the same answers)
     check(lsm_db_get(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
                      (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)nlog, d_mem_index, ib,
                      (const uint8_t *)d_img, d_index, level_start, (const uint64_t *)d_off,
                      (const uint64_t *)d_len, (const lsm_sst_meta *)d_meta, nullptr,
                      (const lsm_rec_desc *)d_idesc, (const int64_t *)d_ival, nullptr, 0, 0,
-                     (const uint8_t *)d_keys, (const uint64_t *)d_koff, nkeys, mode, (int32_t *)d_res,
+                     (const uint8_t *)k.d_bytes, (const uint64_t *)k.d_off, nkeys, mode, (int32_t *)d_res,
                      (int32_t *)d_log, (uint32_t *)d_slot, (int32_t *)d_level, (int32_t *)d_table,
                      (int32_t *)d_tres, (lsm_rec_desc *)d_val, (int32_t *)d_src, d_ws, ws, d.stream()),
           "lsm_db_get");
@@ -1357,12 +1375,7 @@ std::vector<ScanResult> ScanFromWALs(const std::vector<Bytes> &wals, const std::
     size_t ib = 0;
     if (nlog) {
         r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
-        ib = lsm_memtable_search_index_bytes(r.nslot);
-        d_mem_index = d.Dev(16, ib);
-        check(lsm_memtable_search_index_build(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc,
-                                              (const uint32_t *)r.d_idx, r.d_fsc, (uint32_t)nlog, r.nslot,
-                                              d_mem_index, ib, d.stream()),
-              "lsm_memtable_search_index_build");
+        d_mem_index = sstable::BuildSearchIndex(d, r, &ib);
     }
     // the tree (slots 20-28) and its Seek tree (slot 29), sized for the largest table
     const sstable::DeviceTree t = sstable::UploadTree(d, images);
@@ -1384,72 +1397,40 @@ std::vector<ScanResult> ScanFromWALs(const std::vector<Bytes> &wals, const std::
                   "lsm_level_get_tree_build");
         }
     }
-    // the ranges (slots 10-14) and the outputs (15, 30-36)
-    std::vector<uint64_t> lo_off(nq + 1, 0), hi_off(nq + 1, 0);
-    for (size_t q = 0; q < nq; q++) {
-        lo_off[q + 1] = lo_off[q] + ranges[q].lo.size();
-        hi_off[q + 1] = hi_off[q] + ranges[q].hi.size();
-    }
-    uint8_t *h_lo = (uint8_t *)d.Host(1, pad16(lo_off[nq]));
-    uint8_t *h_hi = (uint8_t *)d.Host(3, pad16(hi_off[nq]));
-    uint8_t *h_flags = (uint8_t *)d.Host(4, pad16(nq));
-    std::memset(h_lo, 0, pad16(lo_off[nq]));
-    std::memset(h_hi, 0, pad16(hi_off[nq]));
-    std::memset(h_flags, 0, pad16(nq));
-    for (size_t q = 0; q < nq; q++) {
-        std::memcpy(h_lo + lo_off[q], ranges[q].lo.data(), ranges[q].lo.size());
-        std::memcpy(h_hi + hi_off[q], ranges[q].hi.data(), ranges[q].hi.size());
-        h_flags[q] = ranges[q].no_upper ? LSM_SCAN_NO_UPPER : 0;
-    }
+    // the ranges (slots 10-14), the outputs (15, 30-34, 36) and the workspace (35)
     const size_t n = nq * (size_t)limit;
-    void *d_lo = d.Dev(10, pad16(lo_off[nq])), *d_lo_off = d.Dev(11, (nq + 1) * 8);
-    void *d_hi = d.Dev(12, pad16(hi_off[nq])), *d_hi_off = d.Dev(13, (nq + 1) * 8);
-    void *d_flags = d.Dev(14, pad16(nq));
-    void *d_count = d.Dev(15, nq * 4), *d_more = d.Dev(30, pad16(nq));
-    void *d_key = d.Dev(31, n * sizeof(lsm_rec_desc)), *d_value = d.Dev(32, n * sizeof(lsm_rec_desc));
-    void *d_table = d.Dev(33, n * 4), *d_result = d.Dev(34, n * 4), *d_src = d.Dev(36, n * 4);
+    sstable::DeviceScan sc(d, ranges, n);
+    void *d_src = d.Dev(36, n * 4);
     const size_t ws = lsm_db_scan_workspace_bytes((uint32_t)nlog, level_start, nq);
     void *d_ws = d.Dev(35, ws ? ws : 16);
-    d.H2D(d_lo, h_lo, pad16(lo_off[nq]));
-    d.H2D(d_lo_off, lo_off.data(), (nq + 1) * 8);
-    d.H2D(d_hi, h_hi, pad16(hi_off[nq]));
-    d.H2D(d_hi_off, hi_off.data(), (nq + 1) * 8);
-    d.H2D(d_flags, h_flags, pad16(nq));
     check(lsm_db_scan(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc, (const uint32_t *)r.d_idx,
                       r.d_fsc, (uint32_t)nlog, d_mem_index, ib, (const uint8_t *)t.d_img, t.d_index, level_start,
                       (const uint64_t *)t.d_off, (const uint64_t *)t.d_len, (const lsm_sst_meta *)t.d_meta, nullptr,
                       (const lsm_rec_desc *)t.d_idesc, (const int64_t *)t.d_ival, d_tree, tree_nidx, tree_bytes,
-                      (const uint8_t *)d_lo, (const uint64_t *)d_lo_off, (const uint8_t *)d_hi,
-                      (const uint64_t *)d_hi_off, (const uint8_t *)d_flags, nq, limit, mode, (uint32_t *)d_count,
-                      (uint8_t *)d_more, (lsm_rec_desc *)d_key, (lsm_rec_desc *)d_value, (int32_t *)d_src,
-                      (int32_t *)d_table, (int32_t *)d_result, d_ws, ws, d.stream()),
+                      (const uint8_t *)sc.lo.d_bytes, (const uint64_t *)sc.lo.d_off, (const uint8_t *)sc.hi.d_bytes,
+                      (const uint64_t *)sc.hi.d_off, (const uint8_t *)sc.d_flags, nq, limit, mode,
+                      (uint32_t *)sc.d_count, (uint8_t *)sc.d_more, (lsm_rec_desc *)sc.d_key,
+                      (lsm_rec_desc *)sc.d_value, (int32_t *)d_src, (int32_t *)sc.d_table, (int32_t *)sc.d_result,
+                      d_ws, ws, d.stream()),
           "lsm_db_scan");
-    std::vector<uint32_t> count(nq);
-    std::vector<uint8_t> more(nq);
-    std::vector<lsm_rec_desc> key(n), value(n);
-    std::vector<int32_t> src(n), table(n), result(n);
-    d.D2H(count.data(), d_count, nq * 4);
-    d.D2H(more.data(), d_more, nq);
-    d.D2H(key.data(), d_key, n * sizeof(lsm_rec_desc));
-    d.D2H(value.data(), d_value, n * sizeof(lsm_rec_desc));
+    std::vector<int32_t> src(n);
+    sc.Read(d);
     d.D2H(src.data(), d_src, n * 4);
-    d.D2H(table.data(), d_table, n * 4);
-    d.D2H(result.data(), d_result, n * 4);
     d.Sync();
     for (size_t q = 0; q < nq; q++) {
-        out[q].more = more[q] != 0;
-        out[q].entries.resize(count[q]);
-        for (uint32_t j = 0; j < count[q]; j++) {
+        out[q].more = sc.more[q] != 0;
+        out[q].entries.resize(sc.count[q]);
+        for (uint32_t j = 0; j < sc.count[q]; j++) {
             const size_t o = q * (size_t)limit + j;
+            const lsm_rec_desc &k = sc.key[o], &v = sc.value[o];
             ScanEntry &e = out[q].entries[j];
             // d_src says which buffer the views are into: the logs or the images
             const uint8_t *base = src[o] == LSM_SRC_MEMTABLE ? r.h : t.h_img;
-            e.key.assign((const char *)base + key[o].rec_off + 4, key[o].key_len);
+            e.key.assign((const char *)base + k.rec_off + 4, k.key_len);
             e.src = src[o];
-            e.table = table[o];
-            e.result = result[o];
-            if (result[o] == LSM_GET_FOUND)
-                e.value.assign(base + value[o].rec_off + 4, base + value[o].rec_off + 4 + value[o].val_len);
+            e.table = sc.table[o];
+            e.result = sc.result[o];
+            if (e.result == LSM_GET_FOUND) e.value.assign(base + v.rec_off + 4, base + v.rec_off + 4 + v.val_len);
         }
     }
     return out;

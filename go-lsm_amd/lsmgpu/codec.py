@@ -685,6 +685,24 @@ SCAN_RAW, SCAN_LIVE = 0, 1  # enum lsm_scan_mode
 SCAN_NO_UPPER = 1           # LSM_SCAN_NO_UPPER, bit 0 of a range's flags
 
 
+def _scan_flags(dev, flags, nq: int) -> torch.Tensor:
+    """A scan's flags on the device: a uint8 tensor as it is, host values uploaded."""
+    if isinstance(flags, torch.Tensor):
+        return flags
+    f = np.zeros(max(nq, 1), np.uint8)
+    f[:nq] = np.asarray(flags, dtype=np.uint8)
+    return torch.from_numpy(f).to(dev)
+
+
+def _scan_outputs(dev, nq: int, limit: int):
+    """-> (count, more, key, value, table, result): a scan's output tensors
+    (tree_scan_into), none of them empty."""
+    n = max(nq * max(limit, 0), 1)
+    i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
+    return (i32(max(nq, 1)), torch.empty(max(nq, 1), dtype=torch.uint8, device=dev), i32((n, 4)), i32((n, 4)),
+            i32(n), i32(n))
+
+
 def tree_scan_workspace(ctx: Context, level_start, nq: int) -> torch.Tensor:
     ls = _level_start(level_start)
     n = int(ctx.lib.lsm_tree_scan_workspace_bytes(ls.ctypes.data, nq))
@@ -729,17 +747,8 @@ def tree_scan(ctx: Context, d_img: torch.Tensor, r: SstDecode, level_start, rang
     on the device.  flags: a uint8 device tensor, or host values to upload."""
     dev = ctx.torch_device
     nq = ranges.n
-    n = max(nq * max(limit, 0), 1)
-    count = torch.empty(max(nq, 1), dtype=torch.int32, device=dev)
-    more = torch.empty(max(nq, 1), dtype=torch.uint8, device=dev)
-    key = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    value = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    table = torch.empty(n, dtype=torch.int32, device=dev)
-    result = torch.empty(n, dtype=torch.int32, device=dev)
-    if not isinstance(flags, torch.Tensor):
-        f = np.zeros(max(nq, 1), np.uint8)
-        f[:nq] = np.asarray(flags, dtype=np.uint8)
-        flags = torch.from_numpy(f).to(dev)
+    count, more, key, value, table, result = _scan_outputs(dev, nq, limit)
+    flags = _scan_flags(dev, flags, nq)
     if index is None:
         index = level_index(ctx, d_img, r, stream=stream)
     if nq:
@@ -1458,14 +1467,9 @@ def db_scan(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrde
     flags: a uint8 device tensor, or host values to upload."""
     dev = ctx.torch_device
     nq = ranges.n
-    n = max(nq * max(limit, 0), 1)
-    i32 = lambda k: torch.empty(k, dtype=torch.int32, device=dev)  # noqa: E731
-    out = DbScan(i32(max(nq, 1)), torch.empty(max(nq, 1), dtype=torch.uint8, device=dev), i32((n, 4)),
-                 i32((n, 4)), i32(n), i32(n), i32(n))
-    if not isinstance(flags, torch.Tensor):
-        f = np.zeros(max(nq, 1), np.uint8)
-        f[:nq] = np.asarray(flags, dtype=np.uint8)
-        flags = torch.from_numpy(f).to(dev)
+    count, more, key, value, table, result = _scan_outputs(dev, nq, limit)
+    out = DbScan(count, more, key, value, torch.empty_like(table), table, result)
+    flags = _scan_flags(dev, flags, nq)
     if index is None and sd.nfile:
         index = level_index(ctx, d_img, sd, stream=stream)
     if nq:
