@@ -1436,6 +1436,119 @@ std::vector<ScanResult> ScanFromWALs(const std::vector<Bytes> &wals, const std::
     return out;
 }
 
+std::vector<ScanResult> ScanFromWALsPacked(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
+                                           const uint32_t *level_start,
+                                           const std::vector<sstable::ScanRange> &ranges, uint32_t limit,
+                                           int mode) {
+    if (mode != LSM_SCAN_RAW && mode != LSM_SCAN_LIVE)
+        throw std::invalid_argument("ScanFromWALsPacked: unknown mode");
+    if (limit == 0) throw std::invalid_argument("ScanFromWALsPacked: limit is 0");
+    if (!level_start || level_start[LSM_SEARCH_LEVELS] != images.size())
+        throw std::invalid_argument("ScanFromWALsPacked: level_start does not end at the number of images");
+    const size_t nq = ranges.size(), nlog = wals.size(), nfile = images.size();
+    if ((uint64_t)nq * limit >= (1ull << 32)) throw std::invalid_argument("ScanFromWALsPacked: too many entries");
+    if (nlog > 65535) throw std::invalid_argument("ScanFromWALsPacked: more than 65535 logs");
+    std::vector<ScanResult> out(nq);
+    // no range, or neither a memtable nor a table: nothing in any range; no device call
+    if (nq == 0 || (nlog == 0 && nfile == 0)) return out;
+    Device &d = Device::ThisThread();
+    // the memtables, the tree and its Seek tree: ScanFromWALs's setup, slot for slot
+    sstable::OrderedWALs r{};
+    void *d_mem_index = nullptr;
+    size_t ib = 0;
+    if (nlog) {
+        r = sstable::ReplayAndOrder(d, wals, LSM_MEMTABLE_ALL);
+        d_mem_index = sstable::BuildSearchIndex(d, r, &ib);
+    }
+    const sstable::DeviceTree t = sstable::UploadTree(d, images);
+    void *d_tree = nullptr;
+    uint32_t tree_nidx = 0;
+    size_t tree_bytes = 0;
+    if (nfile) {
+        std::vector<lsm_sst_meta> meta(nfile);
+        d.D2H(meta.data(), t.d_meta, nfile * sizeof(lsm_sst_meta));
+        d.Sync();
+        for (const lsm_sst_meta &m : meta) tree_nidx = std::max(tree_nidx, m.nidx);
+        tree_bytes = lsm_level_get_tree_bytes((uint32_t)nfile, tree_nidx);
+        if (tree_bytes) {
+            d_tree = d.Dev(29, tree_bytes);
+            check(lsm_level_get_tree_build(d.ctx(), (const uint8_t *)t.d_img, (const uint64_t *)t.d_off,
+                                           (const lsm_sst_meta *)t.d_meta, (uint32_t)nfile, nullptr,
+                                           (const lsm_rec_desc *)t.d_idesc, tree_nidx, d_tree, tree_bytes,
+                                           d.stream()),
+                  "lsm_level_get_tree_build");
+        }
+    }
+    const size_t n = nq * (size_t)limit;
+    sstable::DeviceScan sc(d, ranges, n);
+    void *d_src = d.Dev(36, n * 4);
+    const size_t ws = lsm_db_scan_workspace_bytes((uint32_t)nlog, level_start, nq);
+    void *d_ws = d.Dev(35, ws ? ws : 16);
+    check(lsm_db_scan(d.ctx(), (const uint8_t *)r.d_wal, (const lsm_rec_desc *)r.d_desc, (const uint32_t *)r.d_idx,
+                      r.d_fsc, (uint32_t)nlog, d_mem_index, ib, (const uint8_t *)t.d_img, t.d_index, level_start,
+                      (const uint64_t *)t.d_off, (const uint64_t *)t.d_len, (const lsm_sst_meta *)t.d_meta, nullptr,
+                      (const lsm_rec_desc *)t.d_idesc, (const int64_t *)t.d_ival, d_tree, tree_nidx, tree_bytes,
+                      (const uint8_t *)sc.lo.d_bytes, (const uint64_t *)sc.lo.d_off, (const uint8_t *)sc.hi.d_bytes,
+                      (const uint64_t *)sc.hi.d_off, (const uint8_t *)sc.d_flags, nq, limit, mode,
+                      (uint32_t *)sc.d_count, (uint8_t *)sc.d_more, (lsm_rec_desc *)sc.d_key,
+                      (lsm_rec_desc *)sc.d_value, (int32_t *)d_src, (int32_t *)sc.d_table, (int32_t *)sc.d_result,
+                      d_ws, ws, d.stream()),
+          "lsm_db_scan");
+    // the pack (slots 37-44): the sizing call, its counts read back, then the arenas at exactly K and V
+    uint64_t *d_row_start = (uint64_t *)d.Dev(37, (nq + 1) * 8);
+    uint32_t *d_entry_slot = (uint32_t *)d.Dev(38, n * 4);
+    uint64_t *d_koff = (uint64_t *)d.Dev(39, (n + 1) * 8), *d_voff = (uint64_t *)d.Dev(40, (n + 1) * 8);
+    uint64_t *d_counts = (uint64_t *)d.Dev(41, 4 * 8);
+    const size_t pws = lsm_pack_results_workspace_bytes(nq, limit);
+    void *d_pws = d.Dev(42, pws);
+    auto pack = [&](uint8_t *d_keys, uint64_t key_cap, uint8_t *d_vals, uint64_t val_cap) {
+        check(lsm_pack_results(d.ctx(), (const uint8_t *)r.d_wal, (const uint8_t *)t.d_img, (const int32_t *)d_src,
+                               (const lsm_rec_desc *)sc.d_key, (const lsm_rec_desc *)sc.d_value,
+                               (const uint32_t *)sc.d_count, nq, limit, d_keys, key_cap, d_vals, val_cap,
+                               d_row_start, d_entry_slot, d_koff, d_voff, d_counts, d_pws, pws, d.stream()),
+              "lsm_pack_results");
+    };
+    pack(nullptr, 0, nullptr, 0);
+    uint64_t counts[4] = {0, 0, 0, 0};
+    d.D2H(counts, d_counts, sizeof counts);
+    d.Sync();
+    const uint64_t E = counts[0], K = counts[1], V = counts[2];
+    uint8_t *d_keys = (uint8_t *)d.Dev(43, K ? K : 1), *d_vals = (uint8_t *)d.Dev(44, V ? V : 1);
+    pack(d_keys, K, d_vals, V);
+    // one D2H per arena and per side array; the views and the host's logs and images are not consulted
+    std::vector<uint8_t> keys(K), vals(V), more(nq);
+    std::vector<uint64_t> row_start(nq + 1), koff(E + 1), voff(E + 1);
+    std::vector<uint32_t> entry_slot(E);
+    std::vector<int32_t> src(n), table(n), result(n);
+    if (K) d.D2H(keys.data(), d_keys, K);
+    if (V) d.D2H(vals.data(), d_vals, V);
+    d.D2H(row_start.data(), d_row_start, (nq + 1) * 8);
+    if (E) d.D2H(entry_slot.data(), d_entry_slot, E * 4);
+    d.D2H(koff.data(), d_koff, (E + 1) * 8);
+    d.D2H(voff.data(), d_voff, (E + 1) * 8);
+    d.D2H(counts, d_counts, sizeof counts);
+    d.D2H(more.data(), sc.d_more, nq);
+    d.D2H(src.data(), d_src, n * 4);
+    d.D2H(table.data(), sc.d_table, n * 4);
+    d.D2H(result.data(), sc.d_result, n * 4);
+    d.Sync();
+    if (counts[3]) throw std::runtime_error("ScanFromWALsPacked: the arenas sized by the sizing call overflowed");
+    for (size_t q = 0; q < nq; q++) {
+        out[q].more = more[q] != 0;
+        out[q].entries.resize(row_start[q + 1] - row_start[q]);
+        for (uint64_t e = row_start[q]; e < row_start[q + 1]; e++) {
+            const size_t o = entry_slot[e];
+            ScanEntry &x = out[q].entries[e - row_start[q]];
+            x.key.assign((const char *)keys.data() + koff[e], koff[e + 1] - koff[e]);
+            x.src = src[o];
+            x.table = table[o];
+            x.result = result[o];
+            if (x.result == LSM_GET_FOUND) x.value.assign(vals.data() + voff[e], vals.data() + voff[e + 1]);
+        }
+    }
+    return out;
+}
+
 WriteResult WriteBatch(const std::vector<WriteOp> &ops, uint64_t mem_size0, uint64_t mem_max,
                        const Bytes &current_wal) {
     for (const WriteOp &op : ops)

@@ -88,7 +88,7 @@ class Device {
     void Sync();
 
   private:
-    static constexpr int kSlots = 40;
+    static constexpr int kSlots = 48;
     lsm_ctx *ctx_ = nullptr;
     void *stream_ = nullptr;
     void *dev_[kSlots] = {};
@@ -386,6 +386,17 @@ struct ScanResult {
 std::vector<ScanResult> ScanFromWALs(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
                                      const uint32_t *level_start, const std::vector<sstable::ScanRange> &ranges,
                                      uint32_t limit, int mode = LSM_SCAN_LIVE);
+// ScanFromWALs for a tree that lives on the device: the same calls, then
+// lsm_pack_results (the sizing call, its counts read back, the packing call at
+// exactly K and V bytes).  Every entry's key and value come from the two
+// packed arenas, each copied back with one D2H, as are row_start, entry_slot,
+// koff, voff and the per-slot src / table / result; the views are not copied
+// back and the host's `wals` and `images` are not sliced.  Same results as
+// ScanFromWALs, entry for entry.
+std::vector<ScanResult> ScanFromWALsPacked(const std::vector<Bytes> &wals, const std::vector<Bytes> &images,
+                                           const uint32_t *level_start,
+                                           const std::vector<sstable::ScanRange> &ranges, uint32_t limit,
+                                           int mode = LSM_SCAN_LIVE);
 // database.Put / database.Delete (database/database.go:42-59) of a batch over
 // lsm_db_write: memtable.Manager.Insert / Delete (memtable/manager.go:40-106)
 // applied in order -- CanInsert against sizeInBytes (memtable.go:112-121),

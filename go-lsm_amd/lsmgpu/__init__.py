@@ -25,5 +25,7 @@ from .codec import (  # noqa: F401
     MEM_MISS, MEM_VALUE, MEM_DELETED, DBGET_EXACT, DBGET_TOMBSTONE_HIDES, SRC_NONE, SRC_MEMTABLE,
     SRC_SSTABLE, memtable_search_index, memtable_search, memtable_search_into, DbGet, alloc_db_get, db_get, db_get_into,
     DbScan, db_scan, db_scan_into, db_scan_workspace,
+    Packed, alloc_packed, pack_results, pack_results_into, pack_results_workspace, pack_db_scan, pack_db_get,
+    pack_tree_scan, pack_search,
     OP_PUT, OP_DELETE, MAX_MEMTABLE_SIZE, DbWrite, DbWriteResult, db_write, db_write_into)
 from . import synth  # noqa: F401

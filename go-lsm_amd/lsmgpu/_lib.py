@@ -206,6 +206,16 @@ SIGNATURES = {
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "lsm_pack_results_workspace_bytes": (ctypes.c_size_t, [ctypes.c_uint64, ctypes.c_uint32]),
+    "lsm_pack_results": (ctypes.c_int, [ctypes.c_void_p,
+                                        # the two sources, the views and the rows' counts
+                                        c_u8p, c_u8p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                        c_u32p, ctypes.c_uint64, ctypes.c_uint32,
+                                        # the arenas and their caps
+                                        c_u8p, ctypes.c_uint64, c_u8p, ctypes.c_uint64,
+                                        # row_start, entry_slot, koff, voff, counts
+                                        c_u64p, c_u32p, c_u64p, c_u64p, c_u64p,
+                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "lsm_level_get_tree_bytes": (ctypes.c_size_t, [ctypes.c_uint32, ctypes.c_uint32]),
     "lsm_level_get_tree_build": (ctypes.c_int, [ctypes.c_void_p, c_u8p, c_u64p, ctypes.c_void_p,
                                                 ctypes.c_uint32, c_u64p, ctypes.c_void_p,

@@ -1480,6 +1480,127 @@ def db_scan(ctx: Context, d_wal: torch.Tensor, r: DecodeResult, mo: MemtableOrde
                   out.result[:e])
 
 
+# ---- the answered bytes as CSR arenas (lsm_pack_results) -----------------------
+
+@dataclass
+class Packed:
+    """lsm_pack_results's outputs on the device: row q's entries are
+    [row_start[q], row_start[q + 1]); key e is keys[koff[e] : koff[e + 1]],
+    value e is vals[voff[e] : voff[e + 1]]."""
+    row_start: torch.Tensor             # int64[nrow + 1]
+    entry_slot: Optional[torch.Tensor]  # int32[nrow * limit] (uint32 values): entry e's slot
+    koff: Optional[torch.Tensor]        # int64[nrow * limit + 1]; None when no keys are packed
+    voff: torch.Tensor                  # int64[nrow * limit + 1]
+    keys: Optional[torch.Tensor]        # uint8
+    vals: Optional[torch.Tensor]        # uint8
+    counts: torch.Tensor                # int64[4]: {E, K, V, overflow}
+
+
+def pack_results_workspace(ctx: Context, nrow: int, limit: int) -> torch.Tensor:
+    n = int(ctx.lib.lsm_pack_results_workspace_bytes(nrow, limit))
+    return torch.empty(max(n, 16), dtype=torch.uint8, device=ctx.torch_device)
+
+
+def alloc_packed(ctx: Context, nrow: int, limit: int, key_cap: Optional[int], val_cap: Optional[int],
+                 with_keys: bool = True, entry_slot: bool = True) -> Packed:
+    """Output tensors for pack_results_into.  key_cap / val_cap None: no arena
+    (both None: the sizing call).  with_keys False: no koff either."""
+    dev = ctx.torch_device
+    n = max(nrow * limit, 1)
+    i64 = lambda k: torch.empty(k, dtype=torch.int64, device=dev)  # noqa: E731
+    u8 = lambda k: torch.empty(max(k, 1), dtype=torch.uint8, device=dev)  # noqa: E731
+    return Packed(row_start=i64(max(nrow, 0) + 1),
+                  entry_slot=torch.empty(n, dtype=torch.int32, device=dev) if entry_slot else None,
+                  koff=i64(n + 1) if with_keys else None, voff=i64(n + 1),
+                  keys=u8(key_cap) if (with_keys and key_cap is not None) else None,
+                  vals=u8(val_cap) if val_cap is not None else None, counts=i64(4))
+
+
+def pack_results_into(ctx: Context, d_wal: Optional[torch.Tensor], d_img: Optional[torch.Tensor],
+                      value: torch.Tensor, out: Packed, key: Optional[torch.Tensor] = None,
+                      src: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, *,
+                      nrow: int, limit: int, key_cap: int = 0, val_cap: int = 0,
+                      ws: Optional[torch.Tensor] = None, stream=None) -> None:
+    """lsm_pack_results: the live slots of nrow rows of `limit` slots (slot q *
+    limit + j is live when j < count[q]; count None: all) as dense entries, and
+    their keys (key None: not packed) and values packed into out.keys /
+    out.vals, at most key_cap / val_cap bytes (out.counts[3] = 1 and no byte
+    written when they do not fit).  src int32 per slot picks d_wal
+    (SRC_MEMTABLE) or d_img (SRC_SSTABLE; src None: every slot).  Never
+    synchronises: the counts stay on the device."""
+    if ws is None:
+        ws = pack_results_workspace(ctx, nrow, limit)
+    _lib.check(ctx.lib.lsm_pack_results(
+        ctx.handle, _ptr(d_wal), _ptr(d_img), _ptr(src), _ptr(key), _ptr(value), _ptr(count), nrow, limit,
+        _ptr(out.keys), key_cap, _ptr(out.vals), val_cap, _ptr(out.row_start), _ptr(out.entry_slot),
+        _ptr(out.koff), _ptr(out.voff), _ptr(out.counts), _ptr(ws), ws.numel(), _stream_handle(stream)),
+        "lsm_pack_results")
+
+
+def pack_results(ctx: Context, d_wal: Optional[torch.Tensor], d_img: Optional[torch.Tensor],
+                 value: torch.Tensor, key: Optional[torch.Tensor] = None,
+                 src: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None, *,
+                 nrow: int, limit: int, stream=None) -> Packed:
+    """-> Packed with arenas of exactly K and V bytes.  Two calls: the sizing
+    call, a read-back of its counts, then the packing call.  SYNCHRONISES the
+    stream for that read-back (pack_results_into with caps of the caller's
+    does not).  The offset arrays are cut to E + 1 entries."""
+    dev = ctx.torch_device
+    with_keys = key is not None
+    out = alloc_packed(ctx, nrow, limit, None, None, with_keys=with_keys)
+    if nrow == 0:
+        out.row_start.zero_()
+        out.voff.zero_()
+        out.counts.zero_()
+        if out.koff is not None:
+            out.koff.zero_()
+        E = K = V = 0
+    else:
+        ws = pack_results_workspace(ctx, nrow, limit)
+        pack_results_into(ctx, d_wal, d_img, value, out, key=key, src=src, count=count, nrow=nrow,
+                          limit=limit, ws=ws, stream=stream)
+        if stream is not None:
+            stream.synchronize()
+        E, K, V, _ = (int(x) for x in out.counts.cpu().numpy())  # the read-back (synchronises)
+        out.keys = torch.empty(max(K, 1), dtype=torch.uint8, device=dev) if with_keys else None
+        out.vals = torch.empty(max(V, 1), dtype=torch.uint8, device=dev)
+        pack_results_into(ctx, d_wal, d_img, value, out, key=key, src=src, count=count, nrow=nrow,
+                          limit=limit, key_cap=K, val_cap=V, ws=ws, stream=stream)
+    return Packed(row_start=out.row_start[:nrow + 1], entry_slot=out.entry_slot[:E],
+                  koff=out.koff[:E + 1] if with_keys else None, voff=out.voff[:E + 1],
+                  keys=out.keys[:K] if with_keys and out.keys is not None else None,
+                  vals=out.vals[:V] if out.vals is not None else None, counts=out.counts)
+
+
+def pack_db_scan(ctx: Context, d_wal: Optional[torch.Tensor], d_img: Optional[torch.Tensor], scan: DbScan,
+                 limit: int, stream=None) -> Packed:
+    """pack_results over what db_scan returned (synchronises)."""
+    return pack_results(ctx, d_wal, d_img, scan.value, key=scan.key, src=scan.src, count=scan.count,
+                        nrow=int(scan.count.numel()), limit=limit, stream=stream)
+
+
+def pack_db_get(ctx: Context, d_wal: Optional[torch.Tensor], d_img: Optional[torch.Tensor], get: DbGet,
+                stream=None) -> Packed:
+    """pack_results over what db_get returned: entry e is key e, values only
+    (synchronises)."""
+    return pack_results(ctx, d_wal, d_img, get.value, src=get.src, nrow=int(get.src.numel()), limit=1,
+                        stream=stream)
+
+
+def pack_tree_scan(ctx: Context, d_img: torch.Tensor, scan, limit: int, stream=None) -> Packed:
+    """pack_results over the tuple tree_scan returned (synchronises)."""
+    count, _more, key, value = scan[:4]
+    return pack_results(ctx, None, d_img, value, key=key, count=count, nrow=int(count.numel()), limit=limit,
+                        stream=stream)
+
+
+def pack_search(ctx: Context, d_img: torch.Tensor, found, stream=None) -> Packed:
+    """pack_results over the tuple search returned: entry e is key e, values
+    only (synchronises)."""
+    value = found[3]
+    return pack_results(ctx, None, d_img, value, nrow=int(value.shape[0]), limit=1, stream=stream)
+
+
 @dataclass
 class MemtableFlush:
     """memtable_flush's result: image f is out[file_off[f]:file_off[f] +

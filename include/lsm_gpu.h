@@ -59,7 +59,9 @@ extern "C" {
  * lsm_db_get_workspace_bytes (database.Get in one call); lsm_tree_scan and
  * lsm_tree_scan_workspace_bytes (batched range scan over a whole tree);
  * lsm_db_scan and lsm_db_scan_workspace_bytes (that scan with the memtables in
- * front: the batched database scan). */
+ * front: the batched database scan); lsm_pack_results and
+ * lsm_pack_results_workspace_bytes (the answered bytes of those four reads
+ * packed into two CSR arenas on the device). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -842,6 +844,79 @@ int lsm_db_scan(lsm_ctx *ctx,
                 uint32_t *d_count, uint8_t *d_more, lsm_rec_desc *d_key, lsm_rec_desc *d_value,
                 int32_t *d_src, int32_t *d_table, int32_t *d_result,
                 void *d_workspace, size_t ws_bytes, void *stream);
+
+/* The answered bytes of a batched read packed into two CSR arenas, in one
+ * asynchronous call (added within ABI 7): what turns the views lsm_search,
+ * lsm_db_get, lsm_tree_scan and lsm_db_scan return into bytes a host fetches
+ * with two D2H copies, with no host copy of the logs or the images.
+ *   Slots and entries: the input is nrow rows of `limit` slots, slot o = q *
+ *     limit + j.  A slot is live when j < min(d_count[q], limit) (a count above
+ *     limit is clamped); with d_count == NULL every slot is live.  The Get shape
+ *     is nrow = nkeys, limit = 1, d_count = NULL: entry e is key e, whatever it
+ *     answered.  The live slots are numbered densely as entries, rows in order
+ *     and j ascending within a row: d_row_start[q] = the first entry of row q,
+ *     d_row_start[nrow] = E; d_entry_slot[e] = o when that array is given (what
+ *     picks d_table / d_result / d_src for the entries).  The descriptors and
+ *     the source word of a slot that is not live are never read.
+ *   Bytes of an entry: the source is d_src ? d_src[o] : LSM_SRC_SSTABLE, the
+ *     base d_bytes for LSM_SRC_MEMTABLE and d_img for LSM_SRC_SSTABLE.  Any
+ *     other source (LSM_SRC_NONE), or a source whose base is NULL, gives the
+ *     entry a key and a value of length 0; it is still an entry.  Otherwise the
+ *     key is d_key[o].key_len bytes at base + d_key[o].rec_off + 4 (the IDX
+ *     descriptor lsm_tree_scan emits, and the KV descriptor lsm_db_scan emits
+ *     for a memtable node), the value d_value[o].val_len bytes at base +
+ *     d_value[o].rec_off + 4 (lsm_level_get's view).  A zero view (a miss, a
+ *     tombstone of lsm_memtable_search, an error code) packs nothing; a length
+ *     of 0 issues no source load.  d_key == NULL: keys are not packed (d_koff
+ *     and d_keys are not touched, d_counts[1] = 0).
+ *   Offsets and counts: d_koff / d_voff (E + 1 entries written, nrow * limit +
+ *     1 allocated) are the exclusive scans of those lengths over the entries,
+ *     d_koff[E] = K, d_voff[E] = V; key e is d_keys[d_koff[e] .. d_koff[e+1]),
+ *     values alike -- a CSR batch as lsm_encode_blocks or lsm_build_sst_stream
+ *     read.  d_counts = {E, K, V, overflow}.
+ *   Capacity: if d_keys != NULL and K > key_cap, or d_vals != NULL and V >
+ *     val_cap, d_counts[3] = 1 and no byte of either arena is written; the
+ *     offsets, d_row_start, d_entry_slot and d_counts[0..2] are written in full
+ *     all the same.  A NULL arena is skipped and its cap ignored; with both
+ *     NULL the call is the sizing call.  Bytes outside [0, K) of d_keys and
+ *     [0, V) of d_vals are never written: the arenas need no slack.  The
+ *     sources are under the input-slack contract.
+ *   Preconditions: every live view lies inside its buffer (the four producers
+ *     guarantee that); offsets are not validated.  d_keys and d_vals are 16-byte
+ *     aligned, as every device allocation is (the copy stores 16-byte chunks
+ *     aligned in the arena); the sources may have any alignment.
+ * Checks, in this order, all before any launch: ctx == NULL -> LSM_EINVAL; nrow
+ * == 0 -> 0, nothing written; LSM_EINVAL for limit == 0, nrow * limit >= 2^32,
+ * a NULL d_value / d_row_start / d_voff / d_counts, d_key != NULL with d_koff
+ * == NULL, d_keys != NULL with d_key == NULL, d_src == NULL with d_img == NULL;
+ * LSM_ESPACE for a NULL or short workspace.
+ * Workspace, with n = nrow * limit, t = ceil(n / 512) + 1 and r(x) = x rounded
+ * up to 256: lsm_pack_results_workspace_bytes = r(16 * t) + r(8 * t) + 2 * r(8
+ * * n) (the scan's tile sums -- byte sums and live counts -- and each entry's
+ * two source addresses); 0 for nrow == 0 or limit == 0; SIZE_MAX when the
+ * product or the formula leaves 64 bits.
+ * Five launches on the stream, four for the sizing call: the tile sums of
+ * {live, key bytes, value bytes} over the slots, the scan of the tile sums
+ * (two launches: the byte sums, the live counts), the slots' scan (entries,
+ * offsets, row starts, counts and the overflow flag), then the copy, a wave
+ * per 64 entries (it compares the totals with the caps itself).  No host
+ * synchronisation, no read-back, no device allocation, no pointer kept
+ * (capturable). */
+size_t lsm_pack_results_workspace_bytes(uint64_t nrow, uint32_t limit);
+int lsm_pack_results(lsm_ctx *ctx,
+                     const uint8_t *d_bytes,    /* what LSM_SRC_MEMTABLE views point into (may be NULL) */
+                     const uint8_t *d_img,      /* what LSM_SRC_SSTABLE views point into (may be NULL)  */
+                     const int32_t *d_src,      /* per slot, lsm_get_source; NULL = every slot LSM_SRC_SSTABLE */
+                     const lsm_rec_desc *d_key, /* per slot, or NULL: keys are not packed */
+                     const lsm_rec_desc *d_value, /* per slot, required */
+                     const uint32_t *d_count,   /* per row, or NULL: every row holds `limit` live slots */
+                     uint64_t nrow, uint32_t limit,
+                     uint8_t *d_keys, uint64_t key_cap, uint8_t *d_vals, uint64_t val_cap,
+                     uint64_t *d_row_start,     /* nrow + 1 */
+                     uint32_t *d_entry_slot,    /* optional, nrow * limit */
+                     uint64_t *d_koff, uint64_t *d_voff, /* nrow * limit + 1 each; d_koff optional iff d_key == NULL */
+                     uint64_t *d_counts,        /* 4: {entries E, key bytes K, value bytes V, overflow} */
+                     void *d_workspace, size_t ws_bytes, void *stream);
 
 /* database.Put / database.Delete (database/database.go:42-59) of a batch of n
  * operations in one asynchronous call: the write-ahead logs go-lsm would
