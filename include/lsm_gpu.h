@@ -86,6 +86,14 @@ enum lsm_status {
     LSM_ST_CAPACITY = 8,         /* record capacity rec_base[b+1]-rec_base[b] exhausted (not a reference error) */
 };
 
+/* LSM_ST_CAPACITY and a reference error in one block.  A record takes its
+ * slot only after it has passed every check of the reference, and capacity is
+ * raised by the first such record that finds no slot.  So a block (or a log of
+ * lsm_wal_replay) with more valid records than slots reports LSM_ST_CAPACITY
+ * with d_nrec = the capacity, whatever error follows those records; one whose
+ * valid records all fit -- exactly enough slots included -- reports the
+ * reference's own status.  No slot past the capacity is written. */
+
 /* LSM_ST_IDX_OVERRUN and the reference's three messages.  IndexBlock.DecodeFrom
  * (index.go:61-101) reads an entry whole -- Key.DecodeFrom, then the i64
  * offset -- and only then compares totalRead with the size.  Which error Go
