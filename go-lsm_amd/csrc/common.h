@@ -32,6 +32,9 @@ struct lsm_ctx {
     // LSM_TIE_GOHEAP calls that replayed the heap (keys with duplicates;
     // distinct keys skip the replay): lsm_goheap_replays
     uint64_t goheap_replays;
+    // what the last lsm_merge_kvs* call's host code chose for the ordering
+    // stage (host words only, no device work): lsm_merge_plan
+    uint32_t merge_plan[LSM_MERGE_PLAN_WORDS];
 };
 constexpr size_t kHostReadback = 256 * 1024;
 

@@ -1636,6 +1636,12 @@ extern "C" int lsm_goheap_pop_order_host(const uint32_t *rank, uint64_t n, uint3
 
 extern "C" uint64_t lsm_goheap_replays(const lsm_ctx *ctx) { return ctx ? ctx->goheap_replays : 0; }
 
+extern "C" int lsm_merge_plan(const lsm_ctx *ctx, uint32_t *plan) {
+    if (!ctx || !plan) return LSM_EINVAL;
+    for (uint32_t t = 0; t < LSM_MERGE_PLAN_WORDS; t++) plan[t] = ctx->merge_plan[t];
+    return 0;
+}
+
 static_assert(sizeof(MergeFile) == 16, "MergeFile layout");
 static_assert(sizeof(Sum2) == 16, "Sum2 layout");
 
@@ -1782,13 +1788,15 @@ __global__ __launch_bounds__(kKwayThreads) void merge_kway_rank_kernel(const K *
 // w.keys[1] and their indices in w.perm[1] (no <= n / 2).
 template <class K>
 static int merge_path(const MergeWs &w, const MergeIn &m, const SortGroup &g, uint32_t bits,
-                      uint32_t rs, uint32_t re, uint32_t no, uint64_t descents, hipStream_t s) {
+                      uint32_t rs, uint32_t re, uint32_t no, uint64_t descents, hipStream_t s,
+                      uint32_t *others) {
     const uint32_t N = m.n, nrun = re - rs;
     K *run_keys = reinterpret_cast<K *>(w.keys[0]);
     K *ok0 = reinterpret_cast<K *>(w.keys[1]), *ok1 = ok0 + no;
     uint32_t *oi0 = w.perm[1], *oi1 = w.perm[1] + no;
     const bool kway = no && descents + 2 <= kKwayMaxRuns && w.sort_bytes >= 4 * (2 * kKwayMaxRuns + 1);
     uint32_t *list = kway ? static_cast<uint32_t *>(w.sort_tmp) : nullptr;
+    *others = kway ? 1 : no ? 2 : 0;  // lsm_merge_plan's word 2
     hipLaunchKernelGGL(merge_extract_split_kernel<K>, dim3(grid_for(N)), dim3(kMergeThreads), 0, s, m,
                        g, rs, re, run_keys, ok0, oi0, list);
     if (kway) {
@@ -1820,6 +1828,7 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
                      uint64_t *d_counts, void *d_ws, size_t ws_bytes, void *stream,
                      const uint64_t *d_expect_n = nullptr) {
     if (!ctx || (!h_counts && !d_counts) || threshold == 0 || n >= 0xFFFFFFFFull) return LSM_EINVAL;
+    for (uint32_t t = 0; t < LSM_MERGE_PLAN_WORDS; t++) ctx->merge_plan[t] = 0;
     if (tie != LSM_TIE_INPUT && tie != LSM_TIE_GOHEAP) return LSM_EINVAL;
     if (n && (!d_bytes || !d_key_desc || !d_out || !d_ws)) return LSM_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -1910,6 +1919,7 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
     }
     int cur = 0;
     bool have_perm = false;
+    uint32_t plan_width = 0, plan_others = 0, plan_passes = 0;  // lsm_merge_plan
     // the merge path: every varying bit in one packed key and one sorted run
     // holding at least half the pairs
     uint32_t all_bits = 0;
@@ -1923,10 +1933,11 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
             g.field[t] = fields[g.nf - 1 - t].first;
             g.mask[t] = fields[g.nf - 1 - t].second;
         }
-        const int rc = all_bits <= 32
-                           ? merge_path<uint32_t>(w, m, g, all_bits, rs, re, no, descents, s)
-                           : merge_path<uint64_t>(w, m, g, all_bits, rs, re, no, descents, s);
+        const bool path32 = all_bits <= 32;
+        const int rc = path32 ? merge_path<uint32_t>(w, m, g, all_bits, rs, re, no, descents, s, &plan_others)
+                              : merge_path<uint64_t>(w, m, g, all_bits, rs, re, no, descents, s, &plan_others);
         if (rc) return rc;
+        plan_width = path32 ? 32 : 64;
         fields.clear();
         have_perm = true;  // w.perm[0]
     }
@@ -1965,6 +1976,13 @@ static int merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d
         if (e != hipSuccess) return -(1000 + (int)e);
         cur ^= 1;
         f0 = f1;
+        plan_passes++;
+    }
+    {
+        const uint32_t plan[LSM_MERGE_PLAN_WORDS] = {
+            plan_width ? 2u : plan_passes ? 1u : 0u, plan_width, plan_others, plan_passes, D, rs, re,
+            descents > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)descents};
+        for (uint32_t t = 0; t < LSM_MERGE_PLAN_WORDS; t++) ctx->merge_plan[t] = plan[t];
     }
     if (!have_perm)
         hipLaunchKernelGGL(merge_iota_kernel, dim3(grid_for(n)), dim3(kMergeThreads), 0, s,

@@ -61,7 +61,8 @@ extern "C" {
  * lsm_db_scan and lsm_db_scan_workspace_bytes (that scan with the memtables in
  * front: the batched database scan); lsm_pack_results and
  * lsm_pack_results_workspace_bytes (the answered bytes of those four reads
- * packed into two CSR arenas on the device). */
+ * packed into two CSR arenas on the device); lsm_merge_plan (the ordering
+ * plan the last merge call chose, read-only). */
 #define LSM_ABI_VERSION 7
 #define LSM_INPUT_SLACK 32  /* readable bytes past roundup16(n) of any device input */
 
@@ -1143,6 +1144,23 @@ int lsm_merge_kvs_tie(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *
  * counts the replays a context has run. */
 int lsm_goheap_pop_order_host(const uint32_t *rank, uint64_t n, uint32_t *order, uint64_t *phase_ns);
 uint64_t lsm_goheap_replays(const lsm_ctx *ctx);
+/* The ordering plan the host chose in the context's last lsm_merge_kvs /
+ * _tie / _async / lsm_compact_merge_async call, for tests and diagnosis
+ * (read-only; host words kept in the context: no kernel, copy or
+ * synchronisation).  plan[LSM_MERGE_PLAN_WORDS]:
+ *   [0] order kind: 0 = no key bit varies (the identity order), 1 = LSD radix
+ *       passes, 2 = the merge path (one sorted run holds at least half the pairs)
+ *   [1] packed key width of the merge path: 32 or 64; 0 off the merge path
+ *   [2] how the merge path ordered the pairs outside the run: 0 = there were
+ *       none (or no merge path), 1 = k-way rank of their sorted runs, 2 = radix sort
+ *   [3] LSD radix passes over all pairs
+ *   [4] D, the 8-byte chunks of the longest key
+ *   [5], [6] the longest sorted run of the input, [run_s, run_e)
+ *   [7] the input's descents (key(i) < key(i - 1)), saturated at 2^32 - 1
+ * All zero before the first call, after a call with n == 0 and after a call
+ * that failed before it chose.  Returns LSM_EINVAL for a null argument. */
+#define LSM_MERGE_PLAN_WORDS 8
+int lsm_merge_plan(const lsm_ctx *ctx, uint32_t *plan);
 int lsm_merge_kvs(lsm_ctx *ctx, const uint8_t *d_bytes, const lsm_rec_desc *d_key_desc,
                   const lsm_rec_desc *d_val_desc, uint64_t n, int level, uint64_t threshold,
                   uint32_t *d_out, uint64_t *d_file_start, uint64_t *h_counts, void *d_ws,

@@ -39,7 +39,10 @@ def laid_out(name, kv):
 
 
 def upload(ctx, name, kv):
-    buf, kd, vd = laid_out(name, kv)
+    return to_device(ctx, *laid_out(name, kv))
+
+
+def to_device(ctx, buf, kd, vd):
     dev = ctx.torch_device
     d_buf = lsmgpu.to_device_bytes(buf, dev)
     d_kd = torch.from_numpy(kd.view(np.int32).reshape(-1, 4).copy()).to(dev)
@@ -62,7 +65,11 @@ def buffers(ctx, n, ws):
 
 
 def check(name, tie, m, nout, nfiles, max_recs):
-    want, wstarts = expected(name, tie)
+    check_output(*expected(name, tie), m, nout, nfiles, max_recs)
+
+
+def check_output(want, wstarts, m, nout, nfiles, max_recs):
+    """The outputs whole: what the oracle wrote, then the sentinels."""
     out = m.out.cpu().numpy().view(np.uint32)
     starts = m.file_start.cpu().numpy().view(np.uint64)
     assert nfiles == wstarts.size - 1 and nout == want.size, (nfiles, wstarts.size - 1, nout, want.size)
